@@ -10,7 +10,11 @@
 One step = train.py:128-140 of the reference: zero_grad -> STFT features (+PCEN) -> TRU-Net -> phase-aware mask ->
 iSTFT -> L1 + multi-resolution STFT loss -> backward -> gradient all-reduce (N>1) -> grad-norm -> LR schedule ->
 AdamW, on synthetic 64 x 4 s 16 kHz pairs per GPU (weak scaling), fp32, inputs resident in HBM.
-Prints ONE JSON line (rank 0) with the `roofline` and `cpu_baseline` objects described in DESIGN.md.
+Prints ONE JSON line (rank 0).  A plain run only sets up, warms up and times the K steps; `--full` adds what takes runs of
+its own: the `roofline` object (one extra instrumented step), `cpu_baseline` and `other_configs`.
+`--dump-outputs DIR` writes what the last timed step returned (loss terms, gradient norm, gradients, updated parameters
+and BatchNorm statistics; the network output with --streaming) as DIR/<name>.npy; the inputs are seeded, so two builds
+can be compared output for output.
 """
 import argparse
 import json
@@ -169,6 +173,21 @@ def pctl(xs, q):
     return xs[min(len(xs) - 1, max(0, int(round(q * (len(xs) - 1)))))]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: one float32 .npy per named tensor (every output here is a few MB at most, so nothing is sampled)"""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def cpu_baseline(B=8, L=64000, steps=20, warm=2, budget_s=120.0):
     """The reference's CPU path = the oracle (same stock torch.nn / torch.stft calls in the same order,
     SURVEY 8d), timed on this host's cores on a bounded sample of the same workload, B = 8 x 4 s as BASELINE.md section 3
@@ -245,39 +264,45 @@ def streaming(args, dev, emit=True):
                 y = fwd(x)
         torch.cuda.synchronize()
     dt = (time.time() - t0) / args.steps
-    # roofline of the forward kernel: HIP events on the launch stream around direct (un-graphed) calls
+    if args.dump_outputs:
+        outs = {"output": y}
+        if state is not None:
+            outs["tgru_state"] = state.hidden()
+        dump_outputs(args.dump_outputs, outs)
     roof = None
-    with torch.no_grad():
-        evs = []
-        for _ in range(20):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fwd(x)
-            b.record()
-            evs.append((a, b))
-        torch.cuda.synchronize()
-    kms = pctl([a.elapsed_time(b) for a, b in evs], 0.5)
-    flops = streams * (FLOPS_PER_FRAME_STEP / 3.0)            # forward: 31,363,072 flop per frame
-    if args.tgru:       # + one GRU time step per (stream, position): W_ih (384 x 64), W_hh (384 x 128), conv (64 x 128)
-        flops += streams * 2.0 * (384 * 64 + 384 * 128 + 64 * 128) * 16
-    ach = flops / (kms * 1e-3) / 1e12
-    folded = bool(net.__dict__.get("_folded_cache")) and (state is None or state.layout == "folded")
-    from tinyrecurrentunet_amd import export as texport
-    x3 = texport.STREAM_X3
-    roof = {"bound": "mfma", "kernel": ("stream_fwd%s_kernel<%s>" % ("_x3" if x3 else "", "true" if args.tgru else "false")) if folded
-            else "layer-by-layer launches",
-            # priced against the fp32 MFMA peak in fp32-equivalent flops; with the split kernel (the default) the encoder's
-            # pointwise layers -- 42 % of the flops -- run on the bf16 MFMA (six bf16 multiply-adds per fp32 one)
-            "mfma": "fp32, encoder pointwise layers bf16x3" if x3 else "fp32",
-            "achieved": round(ach, 2), "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / PEAK_F32_TFLOPS, 4),
-            "traffic": None, "avg_launch_ms": round(kms, 4),
-            # features in + output out per frame (+ the hidden state read and written: 2 x 8 KB)
-            "algorithmic_bytes_per_launch": streams * (12336 + (16384 if args.tgru else 0)),
-            "note": ("one workgroup per frame through all layers in its own LDS: bound by the fp32 MFMA rate (%s)" % (
-                "34.0 Mflop vs 28.7 KB per frame incl. the hidden state" if args.tgru else
-                "31.4 Mflop vs 12.3 KB per frame"))}
+    if args.full:
+        # roofline of the forward kernel: HIP events on the launch stream around direct (un-graphed) calls
+        with torch.no_grad():
+            evs = []
+            for _ in range(20):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fwd(x)
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+        kms = pctl([a.elapsed_time(b) for a, b in evs], 0.5)
+        flops = streams * (FLOPS_PER_FRAME_STEP / 3.0)            # forward: 31,363,072 flop per frame
+        if args.tgru:       # + one GRU time step per (stream, position): W_ih (384 x 64), W_hh (384 x 128), conv (64 x 128)
+            flops += streams * 2.0 * (384 * 64 + 384 * 128 + 64 * 128) * 16
+        ach = flops / (kms * 1e-3) / 1e12
+        folded = bool(net.__dict__.get("_folded_cache")) and (state is None or state.layout == "folded")
+        from tinyrecurrentunet_amd import export as texport
+        x3 = texport.STREAM_X3
+        roof = {"bound": "mfma", "kernel": ("stream_fwd%s_kernel<%s>" % ("_x3" if x3 else "", "true" if args.tgru else "false")) if folded
+                else "layer-by-layer launches",
+                # priced against the fp32 MFMA peak in fp32-equivalent flops; with the split kernel (the default) the encoder's
+                # pointwise layers -- 42 % of the flops -- run on the bf16 MFMA (six bf16 multiply-adds per fp32 one)
+                "mfma": "fp32, encoder pointwise layers bf16x3" if x3 else "fp32",
+                "achieved": round(ach, 2), "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / PEAK_F32_TFLOPS, 4),
+                "traffic": None, "avg_launch_ms": round(kms, 4),
+                # features in + output out per frame (+ the hidden state read and written: 2 x 8 KB)
+                "algorithmic_bytes_per_launch": streams * (12336 + (16384 if args.tgru else 0)),
+                "note": ("one workgroup per frame through all layers in its own LDS: bound by the fp32 MFMA rate (%s)" % (
+                    "34.0 Mflop vs 28.7 KB per frame incl. the hidden state" if args.tgru else
+                    "31.4 Mflop vs 12.3 KB per frame"))}
     cpu = None
-    if not args.no_cpu_baseline and not args.tgru:
+    if args.full and not args.no_cpu_baseline and not args.tgru:
         from oracle import network_ref as nr
         cores = usable_cores()
         torch.set_num_threads(cores)
@@ -350,6 +375,8 @@ def streaming_audio(args, dev):
             out = st._frame(chunk)
     torch.cuda.synchronize()
     dt = (time.time() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"audio_out": out})
     out_ = {"metric": "streaming audio-in -> audio-out real-time factor (1024 streams x 1 hop of 128 samples)",
             "value": round(streams * 0.008 / dt, 1), "unit": "x real time", "n_gpus": 1, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 4), "higher_is_better": True, "dtype": "f32",
@@ -409,7 +436,7 @@ def other_configs(args, dev, step_factory):
             out[key] = {"error": repr(e)}
     try:
         a2 = copy.copy(args)
-        a2.steps, a2.warmup, a2.no_cpu_baseline, a2.tgru = 200, 3, True, False
+        a2.steps, a2.warmup, a2.no_cpu_baseline, a2.tgru, a2.dump_outputs = 200, 3, True, False, None
         r = streaming(a2, dev, emit=False)
         out["streaming_1024"] = {"value": r["value"], "unit": r["unit"], "ms_per_step": r["ms_per_step"],
                                  "steps": 200, "dtype": "f32", "how": "python bench.py --streaming"}
@@ -426,10 +453,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="utterances per GPU")
     ap.add_argument("--seconds", type=float, default=4.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline (one extra instrumented step), CPU baseline, "
+                         "other_configs; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=20, help="timed steps of the CPU baseline (BASELINE.md: >= 50)")
     ap.add_argument("--cpu-budget", type=float, default=120.0, help="time box of the CPU baseline in seconds")
-    ap.add_argument("--no-extras", action="store_true", help="skip the short bf16 / streaming context measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the short bf16 / streaming context measurements")
     ap.add_argument("--no-stft-loss", action="store_true", help="ablation (BASELINE.json configs[4])")
     ap.add_argument("--no-pcen", action="store_true", help="ablation (BASELINE.json configs[4])")
     ap.add_argument("--host-cores", type=int, default=0,
@@ -509,7 +541,7 @@ def main():
         loss.backward()                        # all-reduce fires inside (N > 1)
         sched.step()
         nsq = opt.step()                       # fused grad-norm + AdamW
-        return loss, nsq
+        return loss, info, nsq
 
     for _ in range(args.warmup):
         step()
@@ -525,7 +557,7 @@ def main():
     t0 = time.time()
     marks[0].record()
     for k in range(args.steps):
-        loss, nsq = step()
+        loss, info, nsq = step()
         marks[k + 1].record()
     host_ms = (time.time() - t0) / args.steps * 1e3      # the host's share: time to ENQUEUE a step (no synchronisation yet)
     sync()
@@ -552,27 +584,38 @@ def main():
     ms = dt / args.steps * 1e3
     total_frames = frames * world
     value = total_frames / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the loss and its terms, the squared gradient norm, the (all-reduced)
+        # gradients, and the model state after the update -- flat, in parameters() / named_buffers() order
+        outs = {"loss": loss.detach().reshape(1), "grad_norm_sq": nsq.reshape(-1)}
+        outs.update({"loss_" + k: v.detach().reshape(1) for k, v in info.items()})
+        outs["gradients"] = torch.cat([p.grad.detach().float().reshape(-1) for p in net.parameters() if p.grad is not None])
+        outs["parameters"] = torch.cat([p.detach().float().reshape(-1) for p in net.parameters()])
+        outs["bn_statistics"] = torch.cat([b.float().reshape(-1) for n, b in net.named_buffers()
+                                           if n.endswith(("running_mean", "running_var"))])
+        dump_outputs(args.dump_outputs, outs)
 
     roof = None
-    # per-kernel timing of one more step with HIP events on the launch stream (torch's current stream).  EVERY rank runs
-    # the step (it contains the gradient all-reduce); only rank 0 instruments it.
-    if rank == 0:
+    # --full: per-kernel timing of one more step with HIP events on the launch stream (torch's current stream).  EVERY
+    # rank runs the step (it contains the gradient all-reduce); only rank 0 instruments it.
+    if args.full and rank == 0:
         engine.PROFILE = prof = {}
         engine.PROFILE_BYTES.clear()
         if os.environ.get("TRUNET_BENCH_LAUNCH_LOG"):
             engine.PROFILE_LOG = []
     bucket = getattr(net, "_grad_bucket", None)
-    if bucket is not None:
+    if args.full and bucket is not None:
         bucket.timing = []                     # HIP events around the exchange step (all-reduce of the flat gradient)
-    step()
-    sync()
-    if bucket is not None and dist_info is not None:
+    if args.full:
+        step()
+        sync()
+    if args.full and bucket is not None and dist_info is not None:
         ar = [a.elapsed_time(b) for a, b in bucket.timing]
         bucket.timing = None
         dist_info["allreduce_ms"] = round(sum(ar), 4) if ar else None
         dist_info["allreduce_in_place"] = bucket.in_place
         dist_info["allreduce_bytes"] = 4 * sum(p.numel() for p in net.parameters() if p.grad is not None)
-    if rank == 0:
+    if args.full and rank == 0:
         engine.PROFILE = None
         if engine.PROFILE_LOG is not None:
             with open(os.environ["TRUNET_BENCH_LAUNCH_LOG"], "w") as f:
@@ -663,7 +706,7 @@ def main():
                 "step_flop_frac_of_peak": round(value / world * FLOPS_PER_FRAME_STEP / 1e12 / PEAK_F32_TFLOPS, 4),
                 "step_hbm_GBps_layer_model": round(value / world * HBM_BYTES_PER_FRAME_STEP / 1e9, 1)}
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras and args.dtype == "f32" and not (
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.dtype == "f32" and not (
             args.tgru or args.no_stft_loss or args.no_pcen) and args.mfma == "bf16x3-bwd":
         def step_factory(precision):
             torch.manual_seed(0)
@@ -678,7 +721,8 @@ def main():
             return step2, frames
         extras = other_configs(args, dev, step_factory)
     if rank == 0:
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(steps=args.cpu_steps, budget_s=args.cpu_budget)
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(steps=args.cpu_steps,
+                                                                                              budget_s=args.cpu_budget)
         out = {"metric": "16 kHz frames/sec (train step)", "value": round(value, 1), "unit": "frames/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
                "ms_per_step_median": round(pctl(step_ms, 0.5), 3), "ms_per_step_p10": round(pctl(step_ms, 0.1), 3),

@@ -26,17 +26,18 @@ cd /tmp && export TMPDIR=/tmp
 P="$GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}"
 mkdir -p "$P"
 B="$GRAFT_REPO_ROOT/bench.py"
-insts() { rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d "$P/insts" -o i -- python3 "$B" --steps 1 --warmup 1 --no-cpu-baseline --no-extras > "$P/insts.log" 2>&1; }
-stream() { rocprofv3 --kernel-trace --stats --output-format csv -d "$P/stream$1" -o s -- python3 "$B" --streaming $2 --steps 300 --no-cpu-baseline > "$P/stream$1.log" 2>&1; }
+RES=$(dirname "$P")                 # the bench lines and the launch log go next to the profile sets
+insts() { rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d "$P/insts" -o i -- python3 "$B" --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras > "$P/insts.log" 2>&1; }
+stream() { rocprofv3 --kernel-trace --stats --output-format csv -d "$P/stream$1" -o s -- python3 "$B" --full --streaming $2 --steps 300 --no-cpu-baseline > "$P/stream$1.log" 2>&1; }
 step "instruction mix" insts
 step "stream stats" stream "" ""
 step "stream tgru stats" stream "_tgru" "--tgru"
 find "$GRAFT_REPO_ROOT/gpurun_out" -name "*kernel_trace.csv" -size +20M -delete
 cd "$GRAFT_REPO_ROOT" || exit 1
-bench() { python bench.py "${@:2}" > "gpurun_out/${TAG}_$1.txt" 2> "gpurun_out/${TAG}_$1.err"; }
+bench() { python bench.py --full "${@:2}" > "$RES/${TAG}_$1.txt" 2> "$RES/${TAG}_$1.err"; }
 step "bench fp32" bench bench; tail -c 600 "gpurun_out/${TAG}_bench.txt"
 # per-launch times and flops of the fp32 step (profiles/*_roofline.md): its own run, the extras of the default line would overwrite the log
-launchlog() { TRUNET_BENCH_LAUNCH_LOG="$GRAFT_REPO_ROOT/gpurun_out/${TAG}_launch_f32.log" python bench.py --no-cpu-baseline --no-extras > /dev/null 2>&1; }
+launchlog() { TRUNET_BENCH_LAUNCH_LOG="$RES/${TAG}_launch_f32.log" python bench.py --full --no-cpu-baseline --no-extras > /dev/null 2>&1; }
 step "launch log" launchlog
 step "bench bf16" bench bench_bf16 --dtype bf16 --no-cpu-baseline; tail -c 400 "gpurun_out/${TAG}_bench_bf16.txt"
 exit $rc

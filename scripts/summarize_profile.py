@@ -49,8 +49,8 @@ def main():
     steps = 5   # --steps 3 --warmup 1 + the instrumented step
     with open(os.path.join(ROOT, "profiles", name + "_summary.md"), "w") as f:
         f.write("# %s\n\n" % title)
-        f.write("Command (GPU box): `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 "
-                "--warmup 1 --no-cpu-baseline`\n(%d steps in the trace).  HBM traffic per kernel: `%s_pmc_traffic.json` "
+        f.write("Command (GPU box): `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 "
+                "--warmup 1 --no-cpu-baseline --no-extras`\n(%d steps in the trace).  HBM traffic per kernel: `%s_pmc_traffic.json` "
                 "(separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes).\n\n" % (steps, name))
         f.write("| kernel | calls | total ms | avg us | % |\n|---|---:|---:|---:|---:|\n")
         for r in rows:
@@ -75,8 +75,8 @@ def main():
                      glob.glob(os.path.join(ROOT, "include", "*.h"))):
         h.update(open(fn, "rb").read())
     json.dump({"csrc_hash": h.hexdigest()[:12],
-               "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 1 "
-                       "--warmup 1` (3 steps incl. the instrumented one); hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per "
+               "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full "
+                       "--steps 1 --warmup 1` (3 steps incl. the instrumented one); hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per "
                        "MI355X_MICROARCH.md (gfx950 FETCH_SIZE counts half of wide streaming reads)",
                "hbm_bytes_per_step": per_step, "kernels": ker},
               open(os.path.join(ROOT, "profiles", name + "_pmc_traffic.json"), "w"), indent=1)
@@ -98,7 +98,7 @@ def main():
                  "wave_issuing": round(v["SQ_ACTIVE_INST_ANY"] / v["SQ_WAVE_CYCLES"], 4),
                  "lds_bank_conflict_cycles": v["SQ_LDS_BANK_CONFLICT"]}
     if sq:
-        json.dump({"note": "rocprofv3 --pmc SQ_* pass over `bench.py --steps 1 --warmup 1`; see scripts/summarize_profile.py "
+        json.dump({"note": "rocprofv3 --pmc SQ_* pass over `bench.py --full --steps 1 --warmup 1`; see scripts/summarize_profile.py "
                            "for the ratios", "kernels": dict(sorted(sq.items(), key=lambda kv: -kv[1]["mfma_pipe_busy"]))},
                   open(os.path.join(ROOT, "profiles", name + "_pmc_sq.json"), "w"), indent=1)
     print("step total %.1f ms, HBM %.1f GB/step" % (tot / 1e6 / steps, per_step / 1e9))

@@ -78,7 +78,7 @@ def test_two_rank_dp_step_matches_mean_of_local_gradients(precision):
 def test_bench_two_ranks_complete_without_deadlock(dtype):
     """bench.py under torch.distributed.run with 2 ranks (both on cuda:0, gloo instead of RCCL: this box has one GPU).
     Guards the control flow of the multi-GPU benchmark: every rank must take part in every step that contains the
-    gradient all-reduce, including the instrumented one after the timed region."""
+    gradient all-reduce, including the instrumented one after the timed region (--full)."""
     import json
     import socket
     import subprocess
@@ -88,7 +88,7 @@ def test_bench_two_ranks_complete_without_deadlock(dtype):
     env = dict(os.environ, TRUNET_BENCH_ONE_DEVICE="1", TRUNET_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "4", "--seconds", "1", "--dtype", dtype]
+           "--warmup", "1", "--batch", "4", "--seconds", "1", "--dtype", dtype, "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -108,7 +108,7 @@ def test_bare_bench_gpus_2_starts_its_own_ranks(dtype):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--seconds", "1", "--dtype", dtype]
+           "--seconds", "1", "--dtype", dtype, "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
