@@ -363,6 +363,24 @@ int trunet_stream_features(float* ring, const float* chunk, float* pcen_M, float
 int trunet_stream_mask_istft(const float* net_out, float* ola, float* out, const float* tw512, int S, float beta, float env,
                              void* stream);
 
+/* ---- offline enhancement of B utterances of any lengths (enhance.py), packed back to back ----
+ * audio holds sum L_b samples (L_b >= 257); sample_off[B+1] (prefix of L_b), frame_off[B+1] (prefix of T_b = 1 + L_b/128)
+ * and pair_off[B+1] (prefix of ceil(T_b/2)) are int64 DEVICE arrays; total_* are their last entries.  Frames are paired
+ * per utterance exactly as the dense entry points pair them, so every utterance's result is bit for bit the dense entry
+ * point's on that utterance alone.  An utterance whose offsets are inconsistent or leave the declared totals is skipped.
+ * trunet_stft_features_ragged: trunet_stft_features per utterance -> feat (sum T, C, 257), mag (sum T, 257) if non-NULL.
+ * trunet_pcen_ragged: trunet_pcen with the smoother restarted at each utterance's first frame.
+ * trunet_mask_istft_ragged: trunet_mask_istft_fwd per utterance without the L1 sums -> audio (sum L) with all L_b samples
+ * of each utterance (torch.istft(..., length = L_b)); frames: scratch (sum T, 512). */
+int trunet_stft_features_ragged(const float* audio, const int64_t* sample_off, const int64_t* frame_off,
+                                const int64_t* pair_off, float* feat, float* mag, const float* tw512, int B,
+                                int64_t total_samples, int64_t total_frames, int64_t total_pairs, int C, void* stream);
+int trunet_pcen_ragged(const float* mag, float* out, const int64_t* frame_off, int B, int64_t total_frames, int out_stride,
+                       float eps, float s, float alpha, float delta, float r, void* stream);
+int trunet_mask_istft_ragged(const float* net_out, float* frames, float* audio, const int64_t* sample_off,
+                             const int64_t* frame_off, const int64_t* pair_off, const float* tw512, int B,
+                             int64_t total_samples, int64_t total_frames, int64_t total_pairs, float beta, void* stream);
+
 /* ---- the train step's loss as util.loss_fn composes it (util.py:239-250, stft_loss.py:141-166), fused (round 4) ----
  * trunet_stft_loss_fwdgrad: trunet_stft_loss_fwd's three sums per frame AND the two coefficient-free gradient frames of the
  * same resolution (fr_sc, fr_mag: (B, frames, win_length)) from one pass: the gradient of a resolution is

@@ -933,6 +933,199 @@ __global__ void phm_bwd_kernel(const float2* __restrict__ m, const float2* __res
     if (ge) ge[i] = rb;
 }
 
+// ---------------------------------------------------------------- ragged (packed) batches: offline enhancement
+// B utterances of any lengths L_b packed back to back: sample_off[B+1] over the audio, frame_off[B+1] over the frames
+// (T_b = 1 + L_b / 128), pair_off[B+1] over the frame PAIRS (ceil(T_b / 2)).  One workgroup per pair, exactly as the
+// dense kernels pair frames 2i and 2i+1 of one utterance (a lone last frame with zeros): a frame's rounding depends on
+// its partner through split_pair / the Hermitian packing, so with the same pairs every frame is bit for bit the one the
+// dense kernels compute for that utterance alone.  A pair never crosses an utterance boundary.
+// The offset tables live on the device and are not trusted: an utterance whose extents do not lie inside the declared
+// totals, or are not consistent with each other, is skipped, so no index derived from them leaves the buffers.
+struct RaggedUtt { int64_t s0, f0; int L, T; };
+
+// largest b in [0, B) with off[b] <= v (off non-decreasing); any b in [0, B) for a corrupt table
+__device__ __forceinline__ int ragged_find(const int64_t* __restrict__ off, int B, int64_t v) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool ragged_utt(const int64_t* __restrict__ so, const int64_t* __restrict__ fo, int b,
+                                           int64_t nS, int64_t nT, RaggedUtt& u) {
+    const int64_t s0 = so[b], s1 = so[b + 1], f0 = fo[b], f1 = fo[b + 1];
+    if (s0 < 0 || s1 > nS || s1 - s0 < NF / 2 + 1 || s1 - s0 > 0x7fffffffLL) return false;
+    if (f0 < 0 || f1 > nT || f1 - f0 != 1 + (s1 - s0) / HOPF) return false;
+    u.s0 = s0; u.f0 = f0; u.L = (int)(s1 - s0); u.T = (int)(f1 - f0);
+    return true;
+}
+
+// workgroup -> (utterance, first frame t0 of its pair); false: inconsistent tables, nothing to do
+__device__ __forceinline__ bool ragged_pair(const int64_t* __restrict__ so, const int64_t* __restrict__ fo,
+                                            const int64_t* __restrict__ po, int B, int64_t nS, int64_t nT, int64_t p,
+                                            RaggedUtt& u, int& t0) {
+    const int b = ragged_find(po, B, p);
+    if (!ragged_utt(so, fo, b, nS, nT, u)) return false;
+    const int64_t p0 = po[b];
+    if (p < p0 || po[b + 1] - p0 != (u.T + 1) / 2 || p - p0 >= (u.T + 1) / 2) return false;
+    t0 = (int)(p - p0) * 2;
+    return true;
+}
+
+// the ragged twin of stft_features_kernel: grid (pairs); feat (sum T, C, 257); mag (optional) (sum T, 257)
+__global__ __launch_bounds__(256) void stft_features_ragged_kernel(const float* __restrict__ audio,
+                                                                   const int64_t* __restrict__ so,
+                                                                   const int64_t* __restrict__ fo,
+                                                                   const int64_t* __restrict__ po, float* __restrict__ feat,
+                                                                   float* __restrict__ mag_out, const cpx* __restrict__ tw,
+                                                                   int B, int64_t nS, int64_t nT, int C) {
+    __shared__ cpx sa[NF], sb[NF];
+    RaggedUtt u;
+    int t0;
+    if (!ragged_pair(so, fo, po, B, nS, nT, blockIdx.x, u, t0)) return;      // uniform over the workgroup
+    const int L = u.L, T = u.T;
+    const float* x = audio + u.s0;
+    for (int i = threadIdx.x; i < NF; i += 256) {
+        const float va = x[reflect_idx(t0 * HOPF + i - NF / 2, L)];
+        const float vb = (t0 + 1 < T) ? x[reflect_idx((t0 + 1) * HOPF + i - NF / 2, L)] : 0.f;
+        sa[i] = make_float2(va, vb);
+    }
+    const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    for (int k = threadIdx.x; k < BINS; k += 256) {
+        cpx X[2];
+        split_pair(Z, k, NF, X[0], X[1]);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int t = t0 + f;
+            if (t >= T) continue;
+            const float re = X[f].x, im = X[f].y;
+            const float mag = sqrtf(re * re + im * im);
+            const float db = 20.f * log10f(fmaxf(mag, 1e-7f)) - 25.f;
+            float nm = ((db + 100.f) / 100.f) * 2.f - 1.f;
+            nm = fminf(fmaxf(nm, -1.f), 1.f);
+            float sn = 0.f, cs = 1.f;
+            if (mag > 0.f) { sn = im / mag; cs = re / mag; }
+            float* o = feat + ((size_t)(u.f0 + t) * C) * BINS + k;
+            o[0] = nm;
+            o[(size_t)(C - 2) * BINS] = sn;
+            o[(size_t)(C - 1) * BINS] = cs;
+            if (mag_out) mag_out[(size_t)(u.f0 + t) * BINS + k] = mag;
+        }
+    }
+}
+
+// pcen_scan_kernel over each utterance's own frames: grid (B, 5); the smoother restarts at M[0] = s x[0] per utterance
+__global__ __launch_bounds__(256) void pcen_scan_ragged_kernel(const float* __restrict__ mag, float* __restrict__ out,
+                                                               const int64_t* __restrict__ fo, int64_t nT, int out_stride,
+                                                               float s) {
+    __shared__ float xs[PCEN_TC][64];
+    const int tid = threadIdx.x;
+    const int kb = blockIdx.y * 64;
+    const int b = blockIdx.x;
+    const int64_t f0 = fo[b], f1 = fo[b + 1];
+    if (f0 < 0 || f1 > nT || f1 <= f0) return;
+    const int64_t T = f1 - f0;
+    const float* x = mag + (size_t)f0 * BINS;
+    float* o = out + (size_t)f0 * out_stride;
+    float M = 0.f;
+    for (int64_t t0 = 0; t0 < T; t0 += PCEN_TC) {
+        const int tc = (int)min((int64_t)PCEN_TC, T - t0);
+        for (int i = tid; i < tc * 64; i += 256) {
+            const int t = i >> 6, k = i & 63;
+            xs[t][k] = (kb + k < BINS) ? x[(size_t)(t0 + t) * BINS + kb + k] : 0.f;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            for (int t = 0; t < tc; ++t) {
+                const float v = xs[t][tid];
+                M = (t0 + t == 0) ? s * v : (1.f - s) * M + s * v;
+                xs[t][tid] = M;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < tc * 64; i += 256) {
+            const int t = i >> 6, k = i & 63;
+            if (kb + k < BINS) o[(size_t)(t0 + t) * out_stride + kb + k] = xs[t][k];
+        }
+        __syncthreads();
+    }
+}
+
+// pcen_pow_kernel with the rows on the x axis (the y axis of a grid stops at 65535 rows): grid (2 * rows)
+__global__ __launch_bounds__(256) void pcen_pow_rows_kernel(const float* __restrict__ mag, float* __restrict__ out,
+                                                            int64_t rows, int out_stride, float eps, float alpha,
+                                                            float delta, float r, float dr) {
+    const int k = (blockIdx.x & 1) * 256 + threadIdx.x;
+    const int64_t row = blockIdx.x >> 1;
+    if (k >= BINS || row >= rows) return;
+    const float v = mag[(size_t)row * BINS + k];
+    float* o = out + (size_t)row * out_stride + k;
+    const float M = *o;
+    *o = pcen_value(v, M, eps, alpha, delta, r, dr);
+}
+
+// the ragged twin of mask_istft_frames_kernel: grid (pairs); net_out (sum T, 8, 257) -> frames (sum T, 512)
+__global__ __launch_bounds__(256) void mask_istft_frames_ragged_kernel(const float* __restrict__ net_out,
+                                                                       float* __restrict__ frames,
+                                                                       const int64_t* __restrict__ so,
+                                                                       const int64_t* __restrict__ fo,
+                                                                       const int64_t* __restrict__ po,
+                                                                       const cpx* __restrict__ tw, int B, int64_t nS,
+                                                                       int64_t nT, float beta) {
+    __shared__ cpx sa[NF], sb[NF];
+    RaggedUtt u;
+    int t0;
+    if (!ragged_pair(so, fo, po, B, nS, nT, blockIdx.x, u, t0)) return;
+    const int T = u.T;
+    for (int k = threadIdx.x; k < BINS; k += 256) {
+        cpx X[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            X[f] = make_float2(0.f, 0.f);
+            const int t = t0 + f;
+            if (t < T) {
+                const MaskVals v = mask_vals(net_out + (size_t)(u.f0 + t) * 8 * BINS + k, BINS, beta);
+                const float M = v.S * v.A;
+                X[f] = make_float2(M * v.cm, M * v.sm);
+            }
+            if (k == 0 || k == NF / 2) X[f].y = 0.f;
+        }
+        sa[k] = make_float2(X[0].x - X[1].y, X[0].y + X[1].x);
+        if (k > 0 && k < NF / 2) sa[NF - k] = make_float2(X[0].x + X[1].y, -X[0].y + X[1].x);
+    }
+    const cpx* z = fft_lds_t<9, true>(sa, sb, tw);
+    for (int i = threadIdx.x; i < NF; i += 256) {
+        const cpx v = z[i];
+        frames[((size_t)u.f0 + t0) * NF + i] = v.x * (1.f / NF);
+        if (t0 + 1 < T) frames[((size_t)u.f0 + t0 + 1) * NF + i] = v.y * (1.f / NF);
+    }
+}
+
+// ola_kernel per packed sample, without the L1 sums, for all L_b samples of each utterance: samples past (T_b - 1) * 128
+// take the same envelope formula (the frames that cover them), which is torch.istft(..., length = L_b)
+__global__ __launch_bounds__(256) void ola_ragged_kernel(const float* __restrict__ frames, float* __restrict__ audio,
+                                                         const int64_t* __restrict__ so, const int64_t* __restrict__ fo,
+                                                         int B, int64_t nS, int64_t nT) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nS) return;
+    RaggedUtt u;
+    const int b = ragged_find(so, B, g);
+    if (!ragged_utt(so, fo, b, nS, nT, u) || g < u.s0) return;
+    const int j = (int)(g - u.s0);
+    if (j >= u.L) return;
+    const int T = u.T;
+    const float* fr = frames + (size_t)u.f0 * NF;
+    const int p = j + NF / 2;
+    int hi = p / HOPF; if (hi > T - 1) hi = T - 1;
+    int lo = (p - NF + HOPF) / HOPF; if (p - NF + 1 <= 0) lo = 0;
+    float s = 0.f;
+    for (int t = lo; t <= hi; ++t) s += fr[(size_t)t * NF + (p - t * HOPF)];
+    s /= (float)(hi - lo + 1);
+    audio[g] = s;
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -1121,5 +1314,50 @@ extern "C" int trunet_phm_fwd(const float* mix_ri, const float* est_ri, float* o
     if (!mix_ri || !est_ri || !out || n <= 0) return TRUNET_EINVAL;
     hipLaunchKernelGGL(phm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, (const float2*)mix_ri,
                        (const float2*)est_ri, out, n, beta);
+    return trunet_launch_status();
+}
+
+// ---------------------------------------------------------------- ragged (packed) batches
+// What the host can see is checked here; the offset tables themselves are checked per utterance on the device.
+// sum T_b = B + sum L_b / 128 with L_b >= 257 (so T_b >= 3); sum ceil(T_b / 2) lies in [sum T / 2, (sum T + B) / 2].
+static bool ragged_totals_ok(int B, int64_t nS, int64_t nT, int64_t nP) {
+    return B > 0 && nS >= (int64_t)B * (NF / 2 + 1) && nS <= (int64_t)0x7fffffff * 256 && nT >= 3LL * B &&
+           nT <= nS / HOPF + B && 2 * nP >= nT && 2 * nP <= nT + B && nP <= 0x7fffffff;
+}
+
+extern "C" int trunet_stft_features_ragged(const float* audio, const int64_t* sample_off, const int64_t* frame_off,
+                                           const int64_t* pair_off, float* feat, float* mag, const float* tw512, int B,
+                                           int64_t total_samples, int64_t total_frames, int64_t total_pairs, int C,
+                                           void* stream) {
+    if (!audio || !sample_off || !frame_off || !pair_off || !feat || !tw512 || (C != 3 && C != 4) ||
+        !ragged_totals_ok(B, total_samples, total_frames, total_pairs))
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stft_features_ragged_kernel, dim3((unsigned)total_pairs), dim3(256), 0, ST, audio, sample_off,
+                       frame_off, pair_off, feat, mag, (const cpx*)tw512, B, total_samples, total_frames, C);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_pcen_ragged(const float* mag, float* out, const int64_t* frame_off, int B, int64_t total_frames,
+                                  int out_stride, float eps, float s, float alpha, float delta, float r, void* stream) {
+    if (!mag || !out || !frame_off || B <= 0 || total_frames < B || total_frames > 0x3fffffff || out_stride < BINS)
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(pcen_scan_ragged_kernel, dim3(B, (BINS + 63) / 64), dim3(256), 0, ST, mag, out, frame_off,
+                       total_frames, out_stride, s);
+    hipLaunchKernelGGL(pcen_pow_rows_kernel, dim3((unsigned)(2 * total_frames)), dim3(256), 0, ST, mag, out, total_frames,
+                       out_stride, eps, alpha, delta, r, powf(delta, r));
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_mask_istft_ragged(const float* net_out, float* frames, float* audio, const int64_t* sample_off,
+                                        const int64_t* frame_off, const int64_t* pair_off, const float* tw512, int B,
+                                        int64_t total_samples, int64_t total_frames, int64_t total_pairs, float beta,
+                                        void* stream) {
+    if (!net_out || !frames || !audio || !sample_off || !frame_off || !pair_off || !tw512 ||
+        !ragged_totals_ok(B, total_samples, total_frames, total_pairs))
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(mask_istft_frames_ragged_kernel, dim3((unsigned)total_pairs), dim3(256), 0, ST, net_out, frames,
+                       sample_off, frame_off, pair_off, (const cpx*)tw512, B, total_samples, total_frames, beta);
+    hipLaunchKernelGGL(ola_ragged_kernel, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, ST, frames, audio,
+                       sample_off, frame_off, B, total_samples, total_frames);
     return trunet_launch_status();
 }

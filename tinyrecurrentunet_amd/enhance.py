@@ -1,0 +1,300 @@
+"""Offline enhancement of many recordings of any lengths: the role of the reference's ``denoise.py:27-97`` (broken there,
+SURVEY D12).
+
+``enhance(net, xs)`` takes a list of 1-D fp32 cuda tensors (16 kHz, at least 257 samples each) or a padded ``(B, Lmax)``
+tensor with ``lengths`` and returns the denoised audio with exactly each input's length.  Per utterance the result is the
+offline path of ``util.loss_fn`` -- centred rect STFT with reflect padding and PCEN from the utterance's first frame
+(``dataset.py:56-76,246-272``), the network in eval mode, phase-aware mask and ``torch.istft(..., length=L)``
+(``phm.py:31-45``, ``dataset.py:293-296``) -- and does not depend on which other utterances share the call, their order,
+or the chunking of the frames.  A call is
+
+    pack          the utterances back to back + their offset tables (one host -> device copy)
+    features      trunet_stft_features_ragged (+ trunet_pcen_ragged for C_in = 4): one launch each for the whole batch
+    network       eval mode, no autograd, in chunks of at most ``max_frames`` frames
+    back end      trunet_mask_istft_ragged: one launch pair for the whole batch
+    unpack
+
+The network runs the folded single-launch artefact (``path="folded"``, BatchNorm folded, fp32 whatever the net's
+precision) or the layer kernels (``path="layers"``: the net's own precision, eval schedule); the choice is made once per
+call.  Without the time-recurrent block every frame is independent, so a chunk may split an utterance.  With it
+(``use_tgru``) utterances are grouped by length, each group laid out as B_g blocks of T_max frames with zero features
+after each utterance's end and run with ``frames_per_seq = T_max``: exact, since the block is unidirectional and every
+other layer acts per frame with eval BatchNorm.
+
+Command line (the ``denoise.py`` role)::
+
+    python -m tinyrecurrentunet_amd.enhance --checkpoint CKPT --input-size {3,4} [--use-tgru] --in DIR --out DIR
+"""
+import argparse
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from ._lib import check, ptr
+
+N_FFT, HOP, BINS = 512, 128, 257
+MIN_SAMPLES = N_FFT // 2 + 1          # the reflect padding of the first frame needs x[1..256]
+SAMPLE_RATE = 16000
+PCEN = dict(eps=1e-6, s=0.025, alpha=0.98, delta=2.0, r=0.5)     # dataset.py:56 defaults
+# frames per network launch: 8192 = TRUNet.fold_max_frames.  The folded kernel is persistent (one frame per workgroup
+# iteration), so beyond a few thousand frames its rate no longer moves with the chunk size; the layer kernels' activations
+# grow with it (DESIGN section 3d has the measured rates)
+MAX_FRAMES = 8192
+# TGRU groups: an utterance joins the group of the longest one while it has at least this share of its frames
+TGRU_MIN_FILL = 0.75
+PATHS = ("auto", "folded", "layers")
+
+
+def n_frames(length):
+    return 1 + int(length) // HOP
+
+
+def tgru_groups(frames, max_frames=MAX_FRAMES, min_fill=TGRU_MIN_FILL):
+    """Group utterances (frame counts ``frames``) for the time-recurrent block: longest first, a group of B_g utterances
+    padded to its longest T_max holds at most max(max_frames, T_max) frames, and every member has at least
+    ``min_fill * T_max`` frames.  Returns (groups as lists of indices, padding fraction = padded / computed frames)."""
+    order = sorted(range(len(frames)), key=lambda i: (-frames[i], i))
+    groups, cur, tmax = [], [], 0
+    for i in order:
+        t = frames[i]
+        if cur and ((len(cur) + 1) * tmax > max_frames or t < min_fill * tmax):
+            groups.append(cur)
+            cur = []
+        if not cur:
+            tmax = t
+        cur.append(i)
+    if cur:
+        groups.append(cur)
+    computed = sum(len(g) * frames[g[0]] for g in groups)
+    return groups, (1.0 - sum(frames) / computed) if computed else 0.0
+
+
+def _inputs(x, lengths):
+    """-> (list of 1-D tensors, padded width or None).  Raises before anything reaches the device."""
+    if isinstance(x, (list, tuple)):
+        if lengths is not None:
+            raise ValueError("lengths goes with a padded (B, Lmax) tensor, not with a list")
+        xs = list(x)
+        for b, t in enumerate(xs):
+            if not torch.is_tensor(t) or t.dim() != 1:
+                raise ValueError("utterance %d: expected a 1-D tensor, got %s" % (
+                    b, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        return xs, None
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError("expected a list of 1-D tensors or a (B, Lmax) tensor with lengths")
+    B, width = x.shape
+    if lengths is None:
+        lens = [width] * B
+    else:
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B:
+            raise ValueError("%d lengths for %d rows" % (len(lens), B))
+        for b, n in enumerate(lens):
+            if n > width or n < 0:
+                raise ValueError("lengths[%d] = %d does not fit a row of %d samples" % (b, n, width))
+    return [x[b, :n] for b, n in enumerate(lens)], width
+
+
+@torch.no_grad()
+def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
+    """Denoise recordings of any lengths with ``net`` (a ``network.TRUNet`` in eval mode, on the GPU).
+
+    x: a list of 1-D fp32 cuda tensors -> list of 1-D tensors of the same lengths; or a (B, Lmax) tensor with ``lengths``
+    (default: all Lmax) -> (B, Lmax), zeros past each length.  Every utterance needs at least 257 samples.
+    max_frames: frames per network launch (default 8192; with ``use_tgru`` the frames of one group of equal-ish lengths,
+    a single longer utterance being a group of its own).  path: "folded" (the single-launch eval artefact, fp32), "layers"
+    (the layer kernels in the net's precision) or "auto" (folded unless ``net.fold_eval`` is off; a ``use_tgru`` net
+    always runs the layer kernels, the only ones that carry the block over whole sequences)."""
+    if path not in PATHS:
+        raise ValueError("path must be one of %s, got %r" % (PATHS, path))
+    if max_frames is None:
+        max_frames = MAX_FRAMES
+    if int(max_frames) != max_frames or max_frames < 1:
+        raise ValueError("max_frames must be a positive integer, got %r" % (max_frames,))
+    max_frames = int(max_frames)
+    if net.training:
+        raise L.TrunetHipError("enhance is an inference path: call net.eval() first")
+    if net.use_tgru and path == "folded":
+        raise ValueError("use_tgru runs the layer kernels (frames_per_seq): path='folded' carries no sequence")
+    xs, width = _inputs(x, lengths)
+    for b, t in enumerate(xs):
+        if t.shape[0] < MIN_SAMPLES:
+            raise ValueError("utterance %d has %d samples; at least %d are needed (reflect padding of the first frame)"
+                             % (b, t.shape[0], MIN_SAMPLES))
+    if not xs:
+        return [] if width is None else x.new_zeros((0, width))
+    for b, t in enumerate(xs):
+        if not t.is_cuda:
+            raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: utterance %d is a %s tensor" % (b, t.device))
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: the network sits on %s" % dev)
+    C = net.encoder[0].StandardConv1d[0].in_channels
+    if C not in (3, 4):
+        raise L.TrunetHipError("features have 3 or 4 channels (R2), the network expects %d" % C)
+    if path == "auto":
+        path = "layers" if (net.use_tgru or not net.fold_eval) else "folded"
+
+    # 1. pack
+    pk = Packed(xs, dev)
+    # 2. features (+ PCEN)
+    feat = features(pk, C)
+    # 3. network
+    if net.use_tgru:
+        out = _tgru_forward(net, feat, pk.frames, pk.offs[1], max_frames)
+    else:
+        if path == "folded":
+            run = net.folded()                    # ONE weight check per call (fold_verify), not one per chunk
+        else:
+            if net._engine is None:
+                object.__setattr__(net, "_engine", net._make_engine())
+            eng = net._engine
+            run = lambda v: eng.forward(v, False)[0]
+        if pk.nT <= max_frames:
+            out = run(feat)
+        else:
+            out = torch.cat([run(feat[i:i + max_frames]) for i in range(0, pk.nT, max_frames)])
+    del feat
+    # 4. mask + iSTFT
+    den = mask_istft(pk, out, beta)
+    # 5. unpack
+    if width is None:
+        return list(torch.split(den, pk.lens))
+    Y = torch.zeros((pk.B, width), device=dev, dtype=torch.float32)
+    for b, (s0, n) in enumerate(zip(pk.offs[0, :-1].tolist(), pk.lens)):
+        Y[b, :n] = den[s0:s0 + n]
+    return Y
+
+
+class Packed:
+    """B utterances back to back on ``dev`` (``audio``, sum L_b samples) and their int64 offset tables: rows of ``offs``
+    (host) / ``offs_d`` (device, one copy) = prefix sums of L_b, of T_b = 1 + L_b // 128 and of ceil(T_b / 2)."""
+
+    def __init__(self, xs, dev):
+        self.lens = [int(t.shape[0]) for t in xs]
+        self.frames = [n_frames(n) for n in self.lens]
+        self.B = len(xs)
+        offs = np.zeros((3, self.B + 1), dtype=np.int64)
+        offs[0, 1:] = np.cumsum(self.lens)
+        offs[1, 1:] = np.cumsum(self.frames)
+        offs[2, 1:] = np.cumsum([(t + 1) // 2 for t in self.frames])
+        self.offs = offs
+        self.nS, self.nT, self.nP = (int(v) for v in offs[:, -1])
+        self.offs_d = torch.from_numpy(offs).to(dev)
+        self.audio = torch.cat([t.to(device=dev, dtype=torch.float32) for t in xs]).contiguous()
+        self.dev = dev
+
+    def ptrs(self):
+        return tuple(self.offs_d[i].data_ptr() for i in range(3))
+
+
+def features(pk, C):
+    """trunet_stft_features_ragged (+ trunet_pcen_ragged, C = 4): features (sum T_b, C, 257) of every utterance"""
+    lib, st = L.lib(), L.stream()
+    so, fo, po = pk.ptrs()
+    feat = torch.empty((pk.nT, C, BINS), device=pk.dev, dtype=torch.float32)
+    mag = torch.empty((pk.nT, BINS), device=pk.dev, dtype=torch.float32) if C == 4 else None
+    check(lib.trunet_stft_features_ragged(ptr(pk.audio), so, fo, po, ptr(feat), ptr(mag), ptr(L.twiddles(N_FFT, pk.dev)),
+                                          pk.B, pk.nS, pk.nT, pk.nP, C, st), "stft_features_ragged")
+    if C == 4:
+        p = PCEN
+        check(lib.trunet_pcen_ragged(ptr(mag), feat.view(-1)[BINS:].data_ptr(), fo, pk.B, pk.nT, C * BINS, p["eps"],
+                                     p["s"], p["alpha"], p["delta"], p["r"], st), "pcen_ragged")
+    return feat
+
+
+def mask_istft(pk, out, beta=0.5):
+    """trunet_mask_istft_ragged: net output (sum T_b, 8, 257) -> packed denoised audio (sum L_b)"""
+    out = out.contiguous().float()
+    if tuple(out.shape) != (pk.nT, 8, BINS):
+        raise ValueError("expected (%d, 8, %d) net output, got %s" % (pk.nT, BINS, tuple(out.shape)))
+    so, fo, po = pk.ptrs()
+    fr = torch.empty((pk.nT, N_FFT), device=pk.dev, dtype=torch.float32)
+    den = torch.empty(pk.nS, device=pk.dev, dtype=torch.float32)
+    check(L.lib().trunet_mask_istft_ragged(ptr(out), ptr(fr), ptr(den), so, fo, po, ptr(L.twiddles(N_FFT, pk.dev)), pk.B,
+                                           pk.nS, pk.nT, pk.nP, float(beta), L.stream()), "mask_istft_ragged")
+    return den
+
+
+def _tgru_forward(net, feat, frames, frame_off, max_frames):
+    """use_tgru: per group of similar lengths, B_g blocks of T_max frames (zero features after each utterance's end) through
+    net(..., frames_per_seq=T_max); the padding frames are dropped."""
+    nT, C = feat.shape[0], feat.shape[1]
+    out = torch.empty((nT, 8, BINS), device=feat.device, dtype=torch.float32)
+    groups, _ = tgru_groups(frames, max_frames)
+    for g in groups:
+        tmax = frames[g[0]]
+        xg = torch.zeros((len(g), tmax, C, BINS), device=feat.device, dtype=torch.float32)
+        for k, b in enumerate(g):
+            f0 = int(frame_off[b])
+            xg[k, :frames[b]] = feat[f0:f0 + frames[b]]
+        yg = net(xg.view(-1, C, BINS), frames_per_seq=tmax).view(len(g), tmax, 8, BINS)
+        for k, b in enumerate(g):
+            f0 = int(frame_off[b])
+            out[f0:f0 + frames[b]] = yg[k, :frames[b]]
+    return out
+
+
+# ---------------------------------------------------------------- command line
+def load_net(checkpoint, input_size, use_tgru=False, device="cuda"):
+    """train.py's {"model_state_dict": ...} pickle or a bare state_dict -> TRUNet in eval mode on ``device``."""
+    from .network import TRUNet
+    ck = torch.load(checkpoint, map_location="cpu", weights_only=True)
+    sd = ck["model_state_dict"] if isinstance(ck, dict) and "model_state_dict" in ck else ck
+    net = TRUNet(input_size=input_size, use_tgru=use_tgru)
+    net.load_state_dict(sd)
+    return net.to(device).eval()
+
+
+def _batches(lens, max_samples):
+    """consecutive files up to max_samples samples per call (a longer file is a call of its own)"""
+    cur, tot = [], 0
+    for i, n in enumerate(lens):
+        if cur and tot + n > max_samples:
+            yield cur
+            cur, tot = [], 0
+        cur.append(i)
+        tot += n
+    if cur:
+        yield cur
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m tinyrecurrentunet_amd.enhance",
+                                 description="Denoise every 16 kHz *.wav of a folder with a trained TRU-Net (HIP, MI355X).")
+    ap.add_argument("--checkpoint", required=True, help="train.py checkpoint ({'model_state_dict': ...}) or a state_dict")
+    ap.add_argument("--input-size", type=int, choices=(3, 4), required=True, help="feature channels the net was trained on")
+    ap.add_argument("--use-tgru", action="store_true", help="the net was trained with the time-recurrent block")
+    ap.add_argument("--in", dest="indir", required=True, help="folder of noisy *.wav (mono, 16 kHz)")
+    ap.add_argument("--out", dest="outdir", required=True, help="folder for the denoised int16 *.wav (same names)")
+    ap.add_argument("--max-seconds", type=float, default=600.0, help="audio per enhance() call (default 600 s)")
+    ap.add_argument("--path", choices=PATHS, default="auto", help="network path (default auto)")
+    args = ap.parse_args(argv)
+
+    from scipy.io.wavfile import write as wavwrite
+    from .dataset import _read_wav
+    names = sorted(f for f in os.listdir(args.indir) if f.lower().endswith(".wav"))
+    xs = []
+    for nm in names:
+        x, sr = _read_wav(os.path.join(args.indir, nm))
+        if sr != SAMPLE_RATE:
+            raise SystemExit("%s: %d Hz; the network runs at %d Hz (no resampling)" % (nm, sr, SAMPLE_RATE))
+        if x.shape[0] < MIN_SAMPLES:
+            raise SystemExit("%s: %d samples, at least %d are needed" % (nm, x.shape[0], MIN_SAMPLES))
+        xs.append(x)
+    net = load_net(args.checkpoint, args.input_size, args.use_tgru)
+    os.makedirs(args.outdir, exist_ok=True)
+    max_samples = max(1, int(math.floor(args.max_seconds * SAMPLE_RATE)))
+    for idx in _batches([x.shape[0] for x in xs], max_samples):
+        ys = enhance(net, [xs[i].cuda() for i in idx], path=args.path)
+        for i, y in zip(idx, ys):
+            q = torch.clamp(torch.round(y * 32768.0), -32768, 32767).to(torch.int16).cpu().numpy()
+            wavwrite(os.path.join(args.outdir, names[i]), SAMPLE_RATE, q)
+    print("%d files -> %s" % (len(names), args.outdir))
+
+
+if __name__ == "__main__":
+    main()

@@ -279,6 +279,11 @@ class TRUNet(nn.Module):
             state = AudioStream(self, chunk.shape[0], tgru=self.use_tgru if tgru is None else tgru)
         return state.push(chunk), state
 
+    def enhance(self, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
+        """Offline enhancement of recordings of any lengths (the role of denoise.py:27-97): see enhance.enhance."""
+        from .enhance import enhance
+        return enhance(self, x, lengths=lengths, beta=beta, max_frames=max_frames, path=path)
+
     def _active_params(self):
         return [p for n, p in self.named_parameters() if self.use_tgru or not n.startswith("TGRU.")]
 
