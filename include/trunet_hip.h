@@ -381,6 +381,29 @@ int trunet_mask_istft_ragged(const float* net_out, float* frames, float* audio, 
                              const int64_t* frame_off, const int64_t* pair_off, const float* tw512, int B,
                              int64_t total_samples, int64_t total_frames, int64_t total_pairs, float beta, void* stream);
 
+/* ---- speech-quality metrics of B clean / estimate pairs of any lengths (evaluate.py), packed back to back ----
+ * Offsets are int64 DEVICE prefix arrays of B+1 entries, total_* their last entries; an utterance whose offsets are
+ * inconsistent with each other or leave the totals is skipped.  No call reads anything back to the host: every buffer is
+ * sized by counts the host knows from the lengths.  Each utterance's results are bit for bit independent of its batch-mates.
+ * trunet_resample_ragged: nsig (1 or 2) planes of total_in samples -> planes of total_out; out_off = prefix of
+ *   ceil(L_b p / q); y[m] = p sum_n taps[m q - n p + half] x[n] over the 2*half+1 taps (scipy.signal.resample_poly with
+ *   that window); p, q <= 64, half <= 4096.
+ * trunet_stoi_ragged: STOI and ESTOI (fp64) and the segment count (int64) per utterance of sig = (2, total_samples), clean
+ *   then estimate at 10 kHz.  sig_off: prefix of R_b; frame_off: of F_b = |range(0, R_b - 256, 128)|; seg_off: of
+ *   max(F_b - 30, 0); chunk_off: of ceil(max(F_b - 30, 0) / 64).  window: 256 floats, band_edges: 16 ints (band k = bins
+ *   [e[k], e[k+1]) of the 512-point FFT), workspace: trunet_stoi_workspace_bytes(B, total_frames, total_segments) bytes.
+ * trunet_si_sdr_ragged: SI-SDR in dB (fp64) per utterance; chunk_off: prefix of ceil(L_b / 16384); partials: 5 doubles per
+ *   chunk. */
+int trunet_resample_ragged(const float* in, float* out, const int64_t* in_off, const int64_t* out_off, const float* taps,
+                           int half, int p, int q, int B, int64_t total_in, int64_t total_out, int nsig, void* stream);
+size_t trunet_stoi_workspace_bytes(int B, int64_t total_frames, int64_t total_segments);
+int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, const int64_t* frame_off, const int64_t* seg_off,
+                       const int64_t* chunk_off, const float* window, const int* band_edges, const float* tw512,
+                       void* workspace, double* stoi, double* estoi, int64_t* segments, int B, int64_t total_samples,
+                       int64_t total_frames, int64_t total_segments, int64_t total_chunks, void* stream);
+int trunet_si_sdr_ragged(const float* clean, const float* estimate, const int64_t* sample_off, const int64_t* chunk_off,
+                         double* partials, double* out, int B, int64_t total_samples, int64_t total_chunks, void* stream);
+
 /* ---- the train step's loss as util.loss_fn composes it (util.py:239-250, stft_loss.py:141-166), fused (round 4) ----
  * trunet_stft_loss_fwdgrad: trunet_stft_loss_fwd's three sums per frame AND the two coefficient-free gradient frames of the
  * same resolution (fr_sc, fr_mag: (B, frames, win_length)) from one pass: the gradient of a resolution is

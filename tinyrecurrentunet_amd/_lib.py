@@ -197,6 +197,10 @@ def _declare(L):
         "trunet_stft_features_ragged": [p, p, p, p, p, p, p, i, i64, i64, i64, i, p],
         "trunet_pcen_ragged": [p, p, p, i, i64, i, f, f, f, f, f, p],
         "trunet_mask_istft_ragged": [p, p, p, p, p, p, p, i, i64, i64, i64, f, p],
+        "trunet_resample_ragged": [p, p, p, p, p, i, i, i, i, i64, i64, i, p],
+        "trunet_stoi_workspace_bytes": [i, i64, i64],
+        "trunet_stoi_ragged": [p] * 12 + [i, i64, i64, i64, i64, p],
+        "trunet_si_sdr_ragged": [p, p, p, p, p, p, i, i64, i64, p],
         "trunet_loss_scratch_bytes": [],
         "trunet_loss_finalize": [C.POINTER(LossArgs), p, p, p, p],
         "trunet_loss_grad_gather": [C.POINTER(LossGatherArgs), p, p, p, p, p, i, i, p],
@@ -238,6 +242,7 @@ def _declare(L):
         fn.restype = C.c_int
     L.trunet_stream_fwd_scratch_floats.restype = C.c_size_t
     L.trunet_loss_scratch_bytes.restype = C.c_size_t
+    L.trunet_stoi_workspace_bytes.restype = C.c_size_t
     L._declared = sorted(sig)
 
 

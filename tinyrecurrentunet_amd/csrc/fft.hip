@@ -8,13 +8,9 @@
 // B[k] = (Z[k] - conj Z[N-k])/(2j)): two STFT frames per transform in the feature / iSTFT kernels,
 // the (predicted, target) pair of one frame in the loss kernels.  All of these stages are HBM-bound.
 #include "common.hpp"
+#include "fft_common.hpp"
 
 namespace {
-
-typedef float2 cpx;
-
-__device__ __forceinline__ cpx cmul(cpx a, cpx b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cpx cconj(cpx a) { return make_float2(a.x, -a.y); }
 
 // In-LDS Stockham autosort FFT of size n = 2^logn by all 256 threads of the block.
 // tw[t] = exp(-2*pi*i*t/n), t < n/2.  inverse => conjugated twiddles (unnormalised).
@@ -72,65 +68,6 @@ __device__ cpx* fft_lds(cpx* a, cpx* b, int n, int logn, const cpx* __restrict__
     return x;
 }
 
-// The same FFT with the size as a COMPILE-TIME constant (n = 2^LOGN, 256 threads): every stage's butterfly count per thread,
-// twiddle stride and index masks fold to constants and the stage loop unrolls.  The STFT-loss kernels run ~400 wave
-// instructions per block and are instruction-issue-bound (82k blocks x 4 waves at n = 512: the generic form above, with its
-// runtime `quarter / ns` divisions and masked index arithmetic, is most of that); round 3.
-template <int LOGN, bool INV>
-__device__ __forceinline__ cpx* fft_lds_t(cpx* a, cpx* b, const cpx* __restrict__ tw) {
-    constexpr int n = 1 << LOGN, half = n >> 1, quarter = n >> 2;
-    cpx* x = a;
-    cpx* y = b;
-    if constexpr (LOGN & 1) {
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < (half + 255) / 256; ++it) {
-            const int j = threadIdx.x + 256 * it;
-            if (half >= 256 || j < half) {
-                const cpx u = x[j], v = x[j + half];
-                y[2 * j] = make_float2(u.x + v.x, u.y + v.y);
-                y[2 * j + 1] = make_float2(u.x - v.x, u.y - v.y);
-            }
-        }
-        cpx* t = x; x = y; y = t;
-    }
-#pragma unroll
-    for (int s = (LOGN & 1); s < LOGN; s += 2) {
-        const int ns = 1 << s;                       // constant after unrolling
-        const int tstep = quarter >> s;
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < (quarter + 255) / 256; ++it) {
-            const int j = threadIdx.x + 256 * it;
-            if (quarter >= 256 || j < quarter) {
-                const int k = j & (ns - 1);
-                const int t1 = k * tstep;
-                cpx w1 = tw[t1], w2 = tw[2 * t1];
-                const int t3 = 3 * t1;
-                cpx w3 = tw[t3 >= half ? t3 - half : t3];
-                if (t3 >= half) { w3.x = -w3.x; w3.y = -w3.y; }
-                if (INV) { w1.y = -w1.y; w2.y = -w2.y; w3.y = -w3.y; }
-                const cpx u0 = x[j];
-                const cpx u1 = cmul(w1, x[j + quarter]);
-                const cpx u2 = cmul(w2, x[j + 2 * quarter]);
-                const cpx u3 = cmul(w3, x[j + 3 * quarter]);
-                const cpx v0 = make_float2(u0.x + u2.x, u0.y + u2.y);
-                const cpx v1 = make_float2(u0.x - u2.x, u0.y - u2.y);
-                const cpx v2 = make_float2(u1.x + u3.x, u1.y + u3.y);
-                const cpx d = make_float2(u1.x - u3.x, u1.y - u3.y);
-                const cpx v3 = INV ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);
-                const int j0 = ((j - k) << 2) + k;
-                y[j0] = make_float2(v0.x + v2.x, v0.y + v2.y);
-                y[j0 + ns] = make_float2(v1.x + v3.x, v1.y + v3.y);
-                y[j0 + 2 * ns] = make_float2(v0.x - v2.x, v0.y - v2.y);
-                y[j0 + 3 * ns] = make_float2(v1.x - v3.x, v1.y - v3.y);
-            }
-        }
-        cpx* t = x; x = y; y = t;
-    }
-    __syncthreads();
-    return x;
-}
 // NI = n / 256 of the STFT-loss kernels -> log2 n (NI = 2, 4, 8); NI = 0: the runtime-sized form
 template <int NI, bool INV>
 __device__ __forceinline__ cpx* fft_lds_ni(cpx* a, cpx* b, int n, int logn, const cpx* __restrict__ tw) {
@@ -149,14 +86,6 @@ __device__ __forceinline__ int reflect_idx(int j, int L) {
 constexpr int NF = 512;      // feature STFT size (dataset.py:133)
 constexpr int HOPF = 128;    // dataset.py:134
 constexpr int BINS = 257;
-
-__device__ __forceinline__ void split_pair(const cpx* Z, int k, int n, cpx& A, cpx& B) {
-    const cpx zk = Z[k];
-    const cpx zn = cconj(Z[(n - k) & (n - 1)]);
-    A = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y + zn.y));
-    // (zk - zn) / (2j) = (-j/2) (zk - zn)
-    B = make_float2(0.5f * (zk.y - zn.y), -0.5f * (zk.x - zn.x));
-}
 
 // ---------------------------------------------------------------- STFT features
 // grid (ceil(T/2), B); feat: (B*T, C, 257); mag (optional): (B, T, 257)
