@@ -481,6 +481,17 @@ int trunet_stream_fwd_x3_mask(void);     /* layer groups on the split path in th
 int trunet_stream_fwd_x3_check(const int32_t* h_offsets, int n_offsets, int64_t blob_numel, int Cin);
 int trunet_stream_fwd_x3(const float* x, float* y, const float* blob, const int32_t* h_offsets, int n_offsets,
                          int64_t blob_numel, float* scratch, const float* h_in, float* h_out, int N, int Cin, void* stream);
+/* The stateless forward on the int8 MFMA (stream_fwd_i8.hip): `blob` is the quantized image of
+ * tinyrecurrentunet_amd/quantize.py, `blob_bytes` long (a multiple of 4), h_offsets its 26 section offsets in 32-bit words
+ * (the 26 sections of trunet_stream_fwd: the matrix layers and W_hh as int8 with per-row fp32 scales, the first conv, the
+ * depthwise convs and the last transposed conv fp32).  Activations are quantized per frame and per layer, so every frame is
+ * independent of its batch-mates.  Same grid and scratch as trunet_stream_fwd; the kernel re-checks the offsets.
+ * trunet_i8_mfma_probe: one 16 x 64 (int8, row-major) by 64 x 16 product through the lane maps the kernel uses -> 16 x 16
+ * int32, for the tests. */
+int trunet_stream_fwd_i8_check(const int32_t* h_offsets, int n_offsets, int64_t blob_bytes, int Cin);
+int trunet_stream_fwd_i8(const float* x, float* y, const void* blob, const int32_t* h_offsets, int n_offsets,
+                         int64_t blob_bytes, float* scratch, int N, int Cin, void* stream);
+int trunet_i8_mfma_probe(const void* a, const void* b, int* c, void* stream);
 
 /* ---- input pipeline on the GPU ----
  * DataAugment.__call__ + the clean/noise mix (dataset.py:116-126, :380) for a whole batch resident in HBM:

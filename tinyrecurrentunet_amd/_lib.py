@@ -216,6 +216,9 @@ def _declare(L):
         "trunet_stream_fwd_x3_mask": [],
         "trunet_stream_fwd_x3_check": [C.POINTER(C.c_int32), i, i64, i],
         "trunet_stream_fwd_x3": [p, p, p, C.POINTER(C.c_int32), i, i64, p, p, p, i, i, p],
+        "trunet_stream_fwd_i8_check": [C.POINTER(C.c_int32), i, i64, i],
+        "trunet_stream_fwd_i8": [p, p, p, C.POINTER(C.c_int32), i, i64, p, i, i, p],
+        "trunet_i8_mfma_probe": [p, p, p, p],
         "trunet_bf16_gemm_nparts": [],
         "trunet_bf16_gemm": [C.POINTER(BGemmArgs), p],
         "trunet_bf16_pack_weight": [p, p, i, i, i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), p],

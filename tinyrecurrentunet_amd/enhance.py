@@ -45,7 +45,7 @@ PCEN = dict(eps=1e-6, s=0.025, alpha=0.98, delta=2.0, r=0.5)     # dataset.py:56
 MAX_FRAMES = 8192
 # TGRU groups: an utterance joins the group of the longest one while it has at least this share of its frames
 TGRU_MIN_FILL = 0.75
-PATHS = ("auto", "folded", "layers")
+PATHS = ("auto", "folded", "layers", "int8")
 
 
 def n_frames(length):
@@ -107,7 +107,8 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
     max_frames: frames per network launch (default 8192; with ``use_tgru`` the frames of one group of equal-ish lengths,
     a single longer utterance being a group of its own).  path: "folded" (the single-launch eval artefact, fp32), "layers"
     (the layer kernels in the net's precision) or "auto" (folded unless ``net.fold_eval`` is off; a ``use_tgru`` net
-    always runs the layer kernels, the only ones that carry the block over whole sequences)."""
+    always runs the layer kernels, the only ones that carry the block over whole sequences); "int8" quantizes the net's
+    current weights once per call (quantize.QuantizedTRUNet, stateless nets only)."""
     if path not in PATHS:
         raise ValueError("path must be one of %s, got %r" % (PATHS, path))
     if max_frames is None:
@@ -117,8 +118,8 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
     max_frames = int(max_frames)
     if net.training:
         raise L.TrunetHipError("enhance is an inference path: call net.eval() first")
-    if net.use_tgru and path == "folded":
-        raise ValueError("use_tgru runs the layer kernels (frames_per_seq): path='folded' carries no sequence")
+    if net.use_tgru and path in ("folded", "int8"):
+        raise ValueError("use_tgru runs the layer kernels (frames_per_seq): path=%r carries no sequence" % path)
     xs, width = _inputs(x, lengths)
     for b, t in enumerate(xs):
         if t.shape[0] < MIN_SAMPLES:
@@ -148,6 +149,9 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
     else:
         if path == "folded":
             run = net.folded()                    # ONE weight check per call (fold_verify), not one per chunk
+        elif path == "int8":
+            from .quantize import QuantizedTRUNet
+            run = QuantizedTRUNet.from_module(net)
         else:
             if net._engine is None:
                 object.__setattr__(net, "_engine", net._make_engine())

@@ -29,7 +29,7 @@ PCEN = dict(eps=1e-6, s=0.025, alpha=0.98, delta=2.0, r=0.5)     # dataset.py:56
 
 
 class AudioStream:
-    def __init__(self, net, streams, tgru=False, beta=0.5, device=None):
+    def __init__(self, net, streams, tgru=False, beta=0.5, device=None, int8=False):
         if net.training:
             raise L.TrunetHipError("AudioStream is an inference path: call net.eval() first")
         dev = device if device is not None else next(net.parameters()).device
@@ -45,7 +45,14 @@ class AudioStream:
         self.feat = z(self.S, self.C, BINS)
         # the exported artefact (BatchNorm folded, export.py) is taken HERE: weights are frozen for the life of a stream (no
         # per-hop cache check of the parameters; a new AudioStream picks up new weights)
-        self.run = net.folded(tgru=self.tgru)
+        # int8=True: the int8 artefact of the same weights (quantize.py; stateless only)
+        if int8:
+            if self.tgru:
+                raise L.TrunetHipError("the int8 artefact covers the stateless forward only: int8=True with tgru=True")
+            from .quantize import QuantizedTRUNet
+            self.run = QuantizedTRUNet.from_module(net)
+        else:
+            self.run = net.folded(tgru=self.tgru)
         self.h = self.run.new_state(self.S, dev) if self.tgru else None      # TGRU state (streams, 128, 16)
         self.tw = L.twiddles(N_FFT, dev)
         self.hops_in = 0                    # hops received
