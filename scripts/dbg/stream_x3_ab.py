@@ -1,5 +1,5 @@
 """A/B of the single-launch eval forward: trunet_stream_fwd (fp32 MFMA) vs trunet_stream_fwd_x3 (bf16 MFMA through the three-term
-split in the layers stream_fwd_x3.hip names): agreement, error of both against the float64 oracle, time per 1024 frames."""
+split in the layer groups of stream_fwd.hip's SFX_MASK): agreement, error of both against the float64 oracle, time per 1024 frames."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

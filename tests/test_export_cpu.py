@@ -178,30 +178,41 @@ def test_tgru_sections_of_the_streaming_artefact():
 def test_section_bounds_check_refuses_truncated_and_foreign_images():
     """the offsets of an artefact are checked against the blob length (host side, no GPU): a truncated blob, an
     offset past the end, a misaligned or negative offset, a wrong C_in or a TGRU state request without the block are
-    TRUNET_EINVAL, not a GPU fault"""
+    TRUNET_EINVAL, not a GPU fault.  The same for the split image (export.x3_image at the library's mask) and its check."""
     import ctypes as C
     net = _net()
     lib = L.lib()
+    mask = lib.trunet_stream_fwd_x3_mask()
 
-    def check(blob, offs, cin):
+    def check(blob, offs, cin, x3):
         arr = (C.c_int32 * len(offs))(*[int(v) for v in offs])
-        return lib.trunet_stream_fwd_check(arr, len(offs), len(blob), cin)
-    for tg in (False, True):
+        fn = lib.trunet_stream_fwd_x3_check if x3 else lib.trunet_stream_fwd_check
+        return fn(arr, len(offs), len(blob), cin)
+
+    def image(tg, x3):
         blob, offs, cin = export.fold(net, tgru=tg)
-        assert check(blob, offs, cin) == L.TRUNET_OK
-        assert check(blob[:len(blob) - 20000], offs, cin) == L.TRUNET_EINVAL          # truncated
-        assert check(blob[:int(offs[20])], offs, cin) == L.TRUNET_EINVAL
-        bad = offs.copy(); bad[7] = len(blob) + 4
-        assert check(blob, bad, cin) == L.TRUNET_EINVAL                               # section past the end
-        bad = offs.copy(); bad[3] += 2
-        assert check(blob, bad, cin) == L.TRUNET_EINVAL                               # not 16-byte aligned
-        bad = offs.copy(); bad[0] = -4
-        assert check(blob, bad, cin) == L.TRUNET_EINVAL
-        assert check(blob, offs[:26], cin) == L.TRUNET_EINVAL                         # the 26-offset v2 layout
-        assert check(blob, offs, 5) == L.TRUNET_EINVAL
+        if x3:
+            blob, offs = export.x3_image(blob, offs, mask)
+        return blob, offs, cin
+    for x3 in (False, True):
+        for tg in (False, True):
+            blob, offs, cin = image(tg, x3)
+            assert check(blob, offs, cin, x3) == L.TRUNET_OK
+            tail = 64 * 256 if x3 else 0              # x3_image's zero tail: the fixed-size fragment requests' over-read
+            assert check(blob[:len(blob) - tail - 20000], offs, cin, x3) == L.TRUNET_EINVAL   # truncated
+            assert check(blob[:int(offs[20])], offs, cin, x3) == L.TRUNET_EINVAL
+            bad = offs.copy(); bad[7] = len(blob) + 4
+            assert check(blob, bad, cin, x3) == L.TRUNET_EINVAL                               # section past the end
+            bad = offs.copy(); bad[3] += 2
+            assert check(blob, bad, cin, x3) == L.TRUNET_EINVAL                               # not 16-byte aligned
+            bad = offs.copy(); bad[0] = -4
+            assert check(blob, bad, cin, x3) == L.TRUNET_EINVAL
+            assert check(blob, offs[:26], cin, x3) == L.TRUNET_EINVAL                         # the 26-offset v2 layout
+            assert check(blob, offs, 5, x3) == L.TRUNET_EINVAL
+        blob, offs, cin = image(False, x3)
+        bad = offs.copy(); bad[28] = 64                                                       # partial TGRU export
+        assert check(blob, bad, cin, x3) == L.TRUNET_EINVAL
     blob, offs, cin = export.fold(net)
-    bad = offs.copy(); bad[28] = 64                                                   # partial TGRU export
-    assert check(blob, bad, cin) == L.TRUNET_EINVAL
     with pytest.raises(L.TrunetHipError):
         export.FoldedTRUNet(blob[:1000], offs, cin, device="cpu")
 

@@ -1,7 +1,7 @@
-"""GPU: trunet_stream_fwd_x3 (stream_fwd_x3.hip: the single-launch eval forward with the encoder's pointwise layers on the bf16 MFMA
-through the exact three-term split of the fp32 operands; the default kernel of export.FoldedTRUNet since round 4) against
-trunet_stream_fwd (fp32 MFMA everywhere) and the float64 oracle: an fp32-grade result -- its error against float64 is the fp32
-kernel's own."""
+"""GPU: trunet_stream_fwd_x3 (stream_fwd_kernel<TG, SFX_MASK> in stream_fwd.hip: the single-launch eval forward with the
+encoder's pointwise layers on the bf16 MFMA through the exact three-term split of the fp32 operands; the default kernel of
+export.FoldedTRUNet since round 4) against trunet_stream_fwd (stream_fwd_kernel<TG, 0>: fp32 MFMA everywhere) and the float64
+oracle: an fp32-grade result -- its error against float64 is the fp32 kernel's own."""
 import numpy as np
 import pytest
 import torch

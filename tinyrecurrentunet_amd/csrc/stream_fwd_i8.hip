@@ -1,6 +1,6 @@
 // Eval-mode TRU-Net forward as ONE launch on the int8 MFMA (v_mfma_i32_16x16x64_i8): the quantized artefact of
-// tinyrecurrentunet_amd/quantize.py.  The frame flow, the LDS regions and the vector-ALU layers are
-// those of stream_fwd.hip (section 3a); what differs is every matrix layer:
+// tinyrecurrentunet_amd/quantize.py.  The frame flow and the vector-ALU layers are those of
+// stream_fwd.hip (section 3a), the LDS regions and helpers shared with it (stream_common.hpp); what differs is every matrix layer:
 //
 //   weights   int8, symmetric, one fp32 scale per output row of the folded matrix, 16-row tiles in fragment order
 //             ([K/64 quads: lane l holds A[row l & 15][k = 64 ks + 16 (l >> 4) + 0..15]][16 scales][16 biases]);
@@ -14,22 +14,15 @@
 // then writes the image over the region it was read from (the layer's output goes to another region, as in the fp32 kernel).
 // The GRU recurrence weights W_hh are int8 with per-row scales too, dequantized once into the registers the fp32 kernel
 // pins them in; the recurrence, the first conv, the depthwise convs and the last 8 -> 8 transposed conv stay fp32.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int SI_T = 256;
-constexpr int SI_R0 = 0, SI_R1A = 18432, SI_R1B = 18432 + 9216, SI_R2 = 36864, SI_ARENA = 40960;   // floats (160 KiB)
-constexpr int SI_XB = SI_R2, SI_W0 = SI_R2 + 1088, SI_DWB = SI_R2 + 2432, SI_GRU = SI_R2 + 3200, SI_RED = SI_R2 + 3584;
-constexpr int SI_SKIP = 8192 + 16384 + 8192 + 8192 + 4096;       // enc0..enc4 per workgroup (floats), as stream_fwd.hip
+constexpr int SI_RED = SF_R2 + 3584;     // the quantizer's per-wave amax (behind stream_common.hpp's GRU state)
 constexpr int SI_NOFF = 26;
 constexpr int SI_PAD = 512;              // words behind the last section: the 3-tap ConvT tiles are requested as 5 quads
-
-__host__ __device__ constexpr int si_ls(int L) { return (L + 8 + 15) / 16 * 16; }
-constexpr int LSA = si_ls(128);          // row stride (floats) of every activation buffer
-constexpr int LSG = si_ls(16);           // ... except the GRU projection [384][32]
 
 // words of one 16-row tile with KS quads of A fragments: the quads, then 16 fp32 row scales and 16 fp32 biases
 __host__ __device__ constexpr long long si_tile(int ks) { return 256LL * ks + 32; }
@@ -57,20 +50,6 @@ __host__ __device__ inline int si_check(const int32_t* o, int n, long long words
         if (a + size[k] + SI_PAD > words) return TRUNET_EINVAL;
     }
     return TRUNET_OK;
-}
-
-__device__ __forceinline__ float si_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float si_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-
-__device__ __forceinline__ float si_dpp_xor1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-}
-
-// opaque thread index: keeps every layer's lane addresses from being hoisted out of the frame loop (section 3a (1))
-__device__ __forceinline__ int si_tid() {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));
-    return t;
 }
 
 // bare `ds_read_b128 v, base offset:imm` for the B operand: the lane's base is opaque, the stream's offsets immediates
@@ -101,8 +80,8 @@ __device__ __forceinline__ void si_load(i32x4* fa, f32x4& sw, f32x4& bb, const u
 template <int NW>
 __device__ __forceinline__ float si_quant(float* lds, int src1, int ls1, int c1, int K1, int src2, int ls2, int K, int NP,
                                           int G, int img, int KST) {
-    const int t = si_tid();
-    const int KG = K >> 2, di = SI_T % NP, dg = SI_T / NP;
+    const int t = sf_tid();
+    const int KG = K >> 2, di = SF_T % NP, dg = SF_T / NP;
     float v[NW][4];
     float m = 0.f;
     {
@@ -171,7 +150,7 @@ template <int KS, int NCT, int TPW, bool SPLIT, bool RELU, bool FULL>
 __device__ __forceinline__ void si_pw(const i32x4* fa, const f32x4* sw, const f32x4* bb, float amax, const float* lds_c,
                                       float* lds, int img, int dst, int lsd, int P, int M) {
     constexpr int KST = 64 * KS + 16;
-    const int tid_ = si_tid();
+    const int tid_ = sf_tid();
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6), q = lane >> 4, j = lane & 15;
     const float sx = amax / 127.f;
     const int ng = (P + 16 * NCT - 1) / (16 * NCT);
@@ -209,7 +188,7 @@ template <int TAPS, int S_, int NCT, bool FULL>
 __device__ __forceinline__ void si_convT(const i32x4* fa, f32x4 sw, f32x4 bb, float amax, float* lds, int img, int dst,
                                          int lsd, int Lout, int p0, int Ln) {
     constexpr int KST = 80, PAD = S_ / 2;
-    const int tid_ = si_tid();
+    const int tid_ = sf_tid();
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6), q = lane >> 4, j = lane & 15;
     const int pend = min(Lout, p0 + Ln);
     const int row = 16 * wave + 4 * q;
@@ -249,77 +228,6 @@ __device__ __forceinline__ void si_convT(const i32x4* fa, f32x4 sw, f32x4 bb, fl
     }
 }
 
-// ---- fp32 helpers, as in stream_fwd.hip
-__device__ __forceinline__ void si_guards(float* lds, int buf, int rows, int ls, int L) {
-    for (int i = si_tid(); i < rows * 8; i += SI_T) {
-        const int r = i >> 3, g = i & 7;
-        lds[buf + r * ls + (g < 4 ? g : L + g)] = 0.f;
-    }
-}
-
-template <int K, int S>
-__device__ __forceinline__ void si_dw(float* lds, int src, int lsi, int dst, int lsd, int wl, int C, int Lout) {
-    constexpr int NQ = (3 * S + K - 1 + K / 2 + 3) / 4 + 1;
-    const int Q = Lout >> 2;
-    for (int o = si_tid(); o < C * Q; o += SI_T) {
-        const int ch = o / Q, j = o - ch * Q;
-        float w[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) w[k] = lds[wl + ch * K + k];
-        const float b = lds[wl + C * K + ch];
-        float in[4 * NQ];
-        const float* ip = lds + src + ch * lsi + 4 + 4 * j * S - 4;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const f32x4 t = *(const f32x4*)(ip + 4 * q);
-            in[4 * q] = t[0]; in[4 * q + 1] = t[1]; in[4 * q + 2] = t[2]; in[4 * q + 3] = t[3];
-        }
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = b;
-#pragma unroll
-            for (int k = 0; k < K; ++k) v = fmaf(w[k], in[4 + e * S + k - K / 2], v);
-            r[e] = fmaxf(v, 0.f);
-        }
-        *(f32x4*)(lds + dst + ch * lsd + 4 + 4 * j) = r;
-    }
-}
-
-__device__ __forceinline__ void si_save(const float* lds, int buf, int ls, float* g, int C, int lq) {
-    for (int i = si_tid(); i < (C << lq); i += SI_T) {
-        const int ch = i >> lq, q = i - (ch << lq);
-        ((f32x4*)g)[i] = *(const f32x4*)(lds + buf + ch * ls + 4 + 4 * q);
-    }
-}
-__device__ __forceinline__ void si_restore_request(f32x4 (&rr)[16], const float* g, int C, int lq) {
-    const int t = si_tid();
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int i = t + SI_T * j;
-        if (i < (C << lq)) rr[j] = ((const f32x4*)g)[i];
-    }
-}
-__device__ __forceinline__ void si_restore_commit(const f32x4 (&rr)[16], float* lds, int buf, int ls, int C, int lq) {
-    const int t = si_tid();
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int i = t + SI_T * j;
-        if (i < (C << lq)) {
-            const int ch = i >> lq, q = i - (ch << lq);
-            *(f32x4*)(lds + buf + ch * ls + 4 + 4 * q) = rr[j];
-        }
-    }
-    si_guards(lds, buf, C, ls, 4 << lq);
-}
-__device__ __forceinline__ void si_restore(float* lds, int buf, int ls, const float* g, int C, int lq) {
-    for (int i = si_tid(); i < (C << lq); i += SI_T) {
-        const int ch = i >> lq, q = i - (ch << lq);
-        *(f32x4*)(lds + buf + ch * ls + 4 + 4 * q) = ((const f32x4*)g)[i];
-    }
-    si_guards(lds, buf, C, ls, 4 << lq);
-}
-
 struct SiArgs {
     const float* x; float* y; const uint32_t* blob; float* scratch;
     long long words;
@@ -330,24 +238,24 @@ enum { O_FIRST = 0, O_PW = 1, O_DW = 6, O_GI = 11, O_WHH = 12, O_FG = 13, O_DPW 
 
 #define SI_SYNC() __syncthreads()
 
-__global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) {
+__global__ __launch_bounds__(SF_T, 1) void stream_fwd_i8_kernel(const SiArgs A) {
     // the device's own bounds check of the section table (uniform: every thread returns before touching memory)
     if (si_check(A.o, SI_NOFF, A.words, A.Cin) != TRUNET_OK) return;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* skip = A.scratch + (size_t)blockIdx.x * SI_SKIP;
+    float* skip = A.scratch + (size_t)blockIdx.x * SF_SKIP;
     float* sk0 = skip, *sk1 = sk0 + 8192, *sk2 = sk1 + 16384, *sk3 = sk2 + 8192, *sk4 = sk3 + 8192;
     const int Cin = A.Cin;
     const float* blobf0 = (const float*)A.blob;
 
-    for (int i = tid; i < 64 * Cin * 5 + 64; i += SI_T) lds[SI_W0 + i] = blobf0[A.o[O_FIRST] + i];
+    for (int i = tid; i < 64 * Cin * 5 + 64; i += SF_T) lds[SF_W0 + i] = blobf0[A.o[O_FIRST] + i];
     float xr[5];
     auto request_x = [&](int nn) __attribute__((always_inline)) {
-        constexpr int LSX = si_ls(257);
+        constexpr int LSX = sf_ls(257);
         const float* xg = A.x + (size_t)nn * Cin * 257;
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
-            const int i = tid + SI_T * j;
+            const int i = tid + SF_T * j;
             const int ch = i / LSX, col = i - ch * LSX - 4;
             xr[j] = (nn < A.N && ch < Cin && col >= 0 && col < 257) ? xg[ch * 257 + col] : 0.f;
         }
@@ -363,25 +271,25 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
         f32x4 sw[6], bb[6];              // their row scales and biases (the lane's 4 rows per tile)
         // ---------------- features -> LDS, first conv (C_in -> 64, k5 s2 p1) + ReLU (fp32)     network.py:9-21
         {
-            constexpr int LSX = si_ls(257);
+            constexpr int LSX = sf_ls(257);
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
-                const int i = tid + SI_T * j;
-                if (i < Cin * LSX) lds[SI_XB + i] = xr[j];
+                const int i = tid + SF_T * j;
+                if (i < Cin * LSX) lds[SF_XB + i] = xr[j];
             }
             SI_SYNC();
-            const int t_ = si_tid();
+            const int t_ = sf_tid();
             const int lo = t_ & 127, cg = __builtin_amdgcn_readfirstlane(t_ >> 7);
             float xin[4][5];
 #pragma unroll
             for (int ci = 0; ci < 4; ++ci)
 #pragma unroll
                 for (int k = 0; k < 5; ++k)
-                    xin[ci][k] = ci < Cin ? lds[SI_XB + ci * LSX + 4 + 2 * lo - 1 + k] : 0.f;
+                    xin[ci][k] = ci < Cin ? lds[SF_XB + ci * LSX + 4 + 2 * lo - 1 + k] : 0.f;
             for (int co = 32 * cg; co < 32 * cg + 32; co += 4) {
                 float v[4];
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) v[jj] = lds[SI_W0 + 64 * Cin * 5 + co + jj];
+                for (int jj = 0; jj < 4; ++jj) v[jj] = lds[SF_W0 + 64 * Cin * 5 + co + jj];
 #pragma unroll
                 for (int ci = 0; ci < 4; ++ci) {
                     if (ci < Cin) {
@@ -389,66 +297,66 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
                         for (int k = 0; k < 5; ++k)
 #pragma unroll
                             for (int jj = 0; jj < 4; ++jj)
-                                v[jj] = fmaf(lds[SI_W0 + (co + jj) * Cin * 5 + ci * 5 + k], xin[ci][k], v[jj]);
+                                v[jj] = fmaf(lds[SF_W0 + (co + jj) * Cin * 5 + ci * 5 + k], xin[ci][k], v[jj]);
                     }
                 }
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) lds[SI_R0 + (co + jj) * LSA + 4 + lo] = fmaxf(v[jj], 0.f);
+                for (int jj = 0; jj < 4; ++jj) lds[SF_R0 + (co + jj) * LSA + 4 + lo] = fmaxf(v[jj], 0.f);
             }
-            si_guards(lds, SI_R0, 64, LSA, 128);
+            sf_guards(lds, SF_R0, 64, LSA, 128);
             SI_SYNC();
-            si_save(lds, SI_R0, LSA, sk0, 64, 5);
+            sf_save(lds, SF_R0, LSA, sk0, 64, 5);
         }
         // ---------------- encoder.1: pw 64 -> 128 (int8), dw k3 s1                              network.py:24-43
         {
             float dwr[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) dwr[j] = blobf[A.o[O_DW] + tid + SI_T * j];
+            for (int j = 0; j < 2; ++j) dwr[j] = blobf[A.o[O_DW] + tid + SF_T * j];
 #pragma unroll
             for (int t = 0; t < 2; ++t) si_load<1>(fa + t, sw[t], bb[t], blob + A.o[O_PW] + (4 * t + wave) * si_tile(1), 1, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am = si_quant<8>(lds, SI_R0, LSA, 0, 64, 0, 0, 64, 128, 0, SI_R0, 80);
-            si_pw<1, 2, 2, false, true, true>(fa, sw, bb, am, lds, lds, SI_R0, SI_R1A, LSA, 128, 128);
-            si_guards(lds, SI_R1A, 128, LSA, 128);
+            const float am = si_quant<8>(lds, SF_R0, LSA, 0, 64, 0, 0, 64, 128, 0, SF_R0, 80);
+            si_pw<1, 2, 2, false, true, true>(fa, sw, bb, am, lds, lds, SF_R0, SF_R1A, LSA, 128, 128);
+            sf_guards(lds, SF_R1A, 128, LSA, 128);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) lds[SI_DWB + tid + SI_T * j] = dwr[j];
+            for (int j = 0; j < 2; ++j) lds[SF_DWB + tid + SF_T * j] = dwr[j];
             SI_SYNC();
-            si_dw<3, 1>(lds, SI_R1A, LSA, SI_R0, LSA, SI_DWB, 128, 128);
-            si_guards(lds, SI_R0, 128, LSA, 128);
+            sf_dw<3, 1>(lds, SF_R1A, LSA, SF_R0, LSA, SF_DWB, 128, 128);
+            sf_guards(lds, SF_R0, 128, LSA, 128);
             SI_SYNC();
-            si_save(lds, SI_R0, LSA, sk1, 128, 5);
+            sf_save(lds, SF_R0, LSA, sk1, 128, 5);
         }
         // ---------------- encoder.2 .. encoder.5: ONE loop body (same load sequence every iteration)
         for (int it = 0; it < 4; ++it) {
             const int L = it == 0 ? 128 : (it <= 2 ? 64 : 32);
             float dwr[3];
 #pragma unroll
-            for (int j = 0; j < 3; ++j) dwr[j] = blobf[A.o[O_DW + 1 + it] + tid + SI_T * j];
+            for (int j = 0; j < 3; ++j) dwr[j] = blobf[A.o[O_DW + 1 + it] + tid + SF_T * j];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
                 si_load<2>(fa + 2 * t, sw[t], bb[t], blob + A.o[O_PW + 1 + it] + (4 * t + wave) * si_tile(2), 2, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am = si_quant<16>(lds, SI_R0, LSA, 0, 128, 0, 0, 128, L, 0, SI_R0, 144);
-            si_pw<2, 2, 2, false, true, true>(fa, sw, bb, am, lds, lds, SI_R0, SI_R1A, LSA, L, 128);
-            si_guards(lds, SI_R1A, 128, LSA, L);
+            const float am = si_quant<16>(lds, SF_R0, LSA, 0, 128, 0, 0, 128, L, 0, SF_R0, 144);
+            si_pw<2, 2, 2, false, true, true>(fa, sw, bb, am, lds, lds, SF_R0, SF_R1A, LSA, L, 128);
+            sf_guards(lds, SF_R1A, 128, LSA, L);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) lds[SI_DWB + tid + SI_T * j] = dwr[j];
+            for (int j = 0; j < 3; ++j) lds[SF_DWB + tid + SF_T * j] = dwr[j];
             SI_SYNC();
-            if (it == 1) si_dw<3, 1>(lds, SI_R1A, LSA, SI_R0, LSA, SI_DWB, 128, 64);
-            else if (it == 3) si_dw<3, 2>(lds, SI_R1A, LSA, SI_R0, LSA, SI_DWB, 128, 16);
-            else si_dw<5, 2>(lds, SI_R1A, LSA, SI_R0, LSA, SI_DWB, 128, L >> 1);
+            if (it == 1) sf_dw<3, 1>(lds, SF_R1A, LSA, SF_R0, LSA, SF_DWB, 128, 64);
+            else if (it == 3) sf_dw<3, 2>(lds, SF_R1A, LSA, SF_R0, LSA, SF_DWB, 128, 16);
+            else sf_dw<5, 2>(lds, SF_R1A, LSA, SF_R0, LSA, SF_DWB, 128, L >> 1);
             const int Lo = it == 1 ? 64 : (L >> 1);
-            si_guards(lds, SI_R0, 128, LSA, Lo);
+            sf_guards(lds, SF_R0, 128, LSA, Lo);
             SI_SYNC();
-            if (it < 3) si_save(lds, SI_R0, LSA, it == 0 ? sk2 : (it == 1 ? sk3 : sk4), 128, it == 2 ? 3 : 4);
+            if (it < 3) sf_save(lds, SF_R0, LSA, it == 0 ? sk2 : (it == 1 ? sk3 : sk4), 128, it == 2 ? 3 : 4);
         }
         // ---------------- FGRU input projection (384 x 128, both directions) over 16 positions: 6 row tiles per wave
 #pragma unroll
         for (int t = 0; t < 6; ++t) si_load<2>(fa + 2 * t, sw[t], bb[t], blob + A.o[O_GI] + (4 * t + wave) * si_tile(2), 2, lane);
         __builtin_amdgcn_sched_barrier(0);
         {
-            const float am = si_quant<2>(lds, SI_R0, LSA, 0, 128, 0, 0, 128, 16, 0, SI_R0, 144);
-            si_pw<2, 1, 6, false, false, true>(fa, sw, bb, am, lds, lds, SI_R0, SI_R1A, LSG, 16, 384);
+            const float am = si_quant<2>(lds, SF_R0, LSA, 0, 128, 0, 0, 128, 16, 0, SF_R0, 144);
+            si_pw<2, 1, 6, false, false, true>(fa, sw, bb, am, lds, lds, SF_R0, SF_R1A, LSG, 16, 384);
         }
         SI_SYNC();
         {
@@ -456,7 +364,7 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
             // lane half kh holds the K-half [32 kh, 32 kh + 32) of the unit's r, z, n rows of W_hh -- int8 in the image
             // ([direction][6 quads: gate g, 16-column half h][128 threads][16 bytes], then scales [2][192], b_hh [2][192]),
             // dequantized once into the registers the recurrence keeps them in
-            const int t_ = si_tid();
+            const int t_ = sf_tid();
             const int d = t_ >> 7, j = (t_ & 127) >> 1, kh = t_ & 1;
             const i32x4* whq = (const i32x4*)(blob + A.o[O_WHH]) + (size_t)d * 6 * 128 + (t_ & 127);
             const float* wsc = blobf + A.o[O_WHH] + 2 * 6 * 128 * 4 + d * 192;
@@ -478,14 +386,14 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
 #pragma unroll
             for (int k = 0; k < 32; ++k) asm volatile("" : "+v"(wr[k]), "+v"(wz[k]), "+v"(wn[k]));
             const float br = bhh[j], bz = bhh[64 + j], bn = bhh[128 + j];
-            float* hs = lds + SI_GRU + d * 128;
+            float* hs = lds + SF_GRU + d * 128;
             if ((t_ & 127) < 64) hs[t_ & 127] = 0.f;
             float hme = 0.f;
             SI_SYNC();
             for (int st = 0; st < 16; ++st) {
                 const int pos = d ? 15 - st : st;
                 const float* hc = hs + (st & 1) * 64 + 32 * kh;
-                const float* gi = lds + SI_R1A + (d * 192 + j) * LSG + 4 + pos;
+                const float* gi = lds + SF_R1A + (d * 192 + j) * LSG + 4 + pos;
                 const float gir = gi[0], giz = gi[64 * LSG], gin = gi[128 * LSG];
                 f32x4 hv[8];
 #pragma unroll
@@ -501,43 +409,43 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
                     n0_ = fmaf(wn[4 * i + 2], hv[i][2], n0_); n1 = fmaf(wn[4 * i + 3], hv[i][3], n1);
                 }
                 float gr = r0 + r1, gz = z0 + z1, gn = n0_ + n1;
-                gr += si_dpp_xor1(gr); gz += si_dpp_xor1(gz); gn += si_dpp_xor1(gn);
-                const float r = si_sigmoid(gir + gr + br);
-                const float z = si_sigmoid(giz + gz + bz);
-                const float nn = si_tanh(fmaf(r, gn + bn, gin));
+                gr += sf_dpp_xor1(gr); gz += sf_dpp_xor1(gz); gn += sf_dpp_xor1(gn);
+                const float r = sf_sigmoid(gir + gr + br);
+                const float z = sf_sigmoid(giz + gz + bz);
+                const float nn = sf_tanh(fmaf(r, gn + bn, gin));
                 hme = (1.f - z) * nn + z * hme;
                 if (kh == 0) {
                     hs[((st + 1) & 1) * 64 + j] = hme;
-                    lds[SI_R0 + (d * 64 + j) * LSA + 4 + pos] = hme;
+                    lds[SF_R0 + (d * 64 + j) * LSA + 4 + pos] = hme;
                 }
                 SI_SYNC();
             }
-            si_guards(lds, SI_R0, 128, LSA, 16);
+            sf_guards(lds, SF_R0, 128, LSA, 16);
             SI_SYNC();
         }
         // ---------------- FGRU.conv (128 -> 64) + BN + ReLU
         {
             si_load<2>(fa, sw[0], bb[0], blob + A.o[O_FG] + wave * si_tile(2), 2, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am = si_quant<2>(lds, SI_R0, LSA, 0, 128, 0, 0, 128, 16, 0, SI_R0, 144);
-            si_pw<2, 1, 1, false, true, true>(fa, sw, bb, am, lds, lds, SI_R0, SI_R1A, LSA, 16, 64);
-            si_guards(lds, SI_R1A, 64, LSA, 16);
+            const float am = si_quant<2>(lds, SF_R0, LSA, 0, 128, 0, 0, 128, 16, 0, SF_R0, 144);
+            si_pw<2, 1, 1, false, true, true>(fa, sw, bb, am, lds, lds, SF_R0, SF_R1A, LSA, 16, 64);
+            sf_guards(lds, SF_R1A, 64, LSA, 16);
             SI_SYNC();
         }
         // ---------------- decoder.0 (FirstTrCNN): pw 64 -> 64, ConvT k3 s2 -> L 31            network.py:60-76
         {
             si_load<1>(fa, sw[0], bb[0], blob + A.o[O_DPW] + wave * si_tile(1), 1, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am = si_quant<1>(lds, SI_R1A, LSA, 0, 64, 0, 0, 64, 16, 0, SI_R1A, 80);
-            si_pw<1, 1, 1, false, true, true>(fa, sw, bb, am, lds, lds, SI_R1A, SI_R1B, LSA, 16, 64);
-            si_guards(lds, SI_R1B, 64, LSA, 16);
+            const float am = si_quant<1>(lds, SF_R1A, LSA, 0, 64, 0, 0, 64, 16, 0, SF_R1A, 80);
+            si_pw<1, 1, 1, false, true, true>(fa, sw, bb, am, lds, lds, SF_R1A, SF_R1B, LSA, 16, 64);
+            sf_guards(lds, SF_R1B, 64, LSA, 16);
             SI_SYNC();
-            si_restore(lds, SI_R0, LSA, sk4, 128, 3);
+            sf_restore(lds, SF_R0, LSA, sk4, 128, 3);
             si_load<3>(fa, sw[0], bb[0], blob + A.o[O_CT] + wave * si_tile(3), 3, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am2 = si_quant<2>(lds, SI_R1B, LSA, 0, 64, 0, 0, 64, 24, 4, SI_R1B, 80);
-            si_convT<3, 2, 1, false>(fa, sw[0], bb[0], am2, lds, SI_R1B, SI_R1A, LSA, 31, 0, 31);
-            si_guards(lds, SI_R1A, 64, LSA, 31);
+            const float am2 = si_quant<2>(lds, SF_R1B, LSA, 0, 64, 0, 0, 64, 24, 4, SF_R1B, 80);
+            si_convT<3, 2, 1, false>(fa, sw[0], bb[0], am2, lds, SF_R1B, SF_R1A, LSA, 31, 0, 31);
+            sf_guards(lds, SF_R1A, 64, LSA, 31);
             SI_SYNC();
         }
         // ---------------- decoder.1 .. decoder.4 (TrCNN): [x1 padded / cropped | skip] -> pw 192 -> 64 -> ConvT
@@ -550,47 +458,47 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
             f32x4 rr[16];
             const float* skn = i == 1 ? sk3 : (i == 2 ? sk2 : (i == 3 ? sk1 : sk0));
             const int skC = i == 4 ? 64 : 128, sklq = i <= 2 ? 4 : 5;
-            si_restore_request(rr, skn, skC, sklq);
+            sf_restore_request(rr, skn, skC, sklq);
             __builtin_amdgcn_sched_barrier(0);
-            const float am = si_quant<24>(lds, SI_R1A, LSA, i == 1 ? 0 : 1, 64, SI_R0, LSA, 192, P, 0, SI_R0, 208);
-            si_pw<3, 2, 1, false, true, true>(fa, sw, bb, am, lds, lds, SI_R0, SI_R1B, LSA, P, 64);
-            si_guards(lds, SI_R1B, 64, LSA, P);
+            const float am = si_quant<24>(lds, SF_R1A, LSA, i == 1 ? 0 : 1, 64, SF_R0, LSA, 192, P, 0, SF_R0, 208);
+            si_pw<3, 2, 1, false, true, true>(fa, sw, bb, am, lds, lds, SF_R0, SF_R1B, LSA, P, 64);
+            sf_guards(lds, SF_R1B, 64, LSA, P);
             SI_SYNC();
             // ConvT fragments: 5 quads requested for the 3-tap layers too (same load sequence); scales behind the taps
             const int taps = (i & 1) ? 5 : 3;
             si_load<5>(fa, sw[0], bb[0], blob + A.o[O_CT + i] + wave * (256 * taps + 32), taps, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am2 = si_quant<9>(lds, SI_R1B, LSA, 0, 64, 0, 0, 64, P + 8, 4, SI_R1B, 80);
+            const float am2 = si_quant<9>(lds, SF_R1B, LSA, 0, 64, 0, 0, 64, P + 8, 4, SF_R1B, 80);
             const int Pn = i <= 2 ? 64 : 128;
-            if (i & 1) si_convT<5, 2, 2, true>(fa, sw[0], bb[0], am2, lds, SI_R1B, SI_R1A, LSA, Lo, 1, Pn);
-            else si_convT<3, 1, 2, true>(fa, sw[0], bb[0], am2, lds, SI_R1B, SI_R1A, LSA, Lo, 1, Pn);
-            si_restore_commit(rr, lds, SI_R0, LSA, skC, sklq);
-            si_guards(lds, SI_R1A, 64, LSA, Lo);
+            if (i & 1) si_convT<5, 2, 2, true>(fa, sw[0], bb[0], am2, lds, SF_R1B, SF_R1A, LSA, Lo, 1, Pn);
+            else si_convT<3, 1, 2, true>(fa, sw[0], bb[0], am2, lds, SF_R1B, SF_R1A, LSA, Lo, 1, Pn);
+            sf_restore_commit(rr, lds, SF_R0, LSA, skC, sklq);
+            sf_guards(lds, SF_R1A, 64, LSA, Lo);
             SI_SYNC();
         }
         {   // ---------------- decoder.5 (LastTrCNN): pw 128 -> 8 (+BN+ReLU, int8), ConvT 8 -> 8 k5 s2 -> 257 (fp32), linear
             si_load<2>(fa, sw[0], bb[0], blob + A.o[O_DPW + 5], 2, lane);
             __builtin_amdgcn_sched_barrier(0);
-            const float am = si_quant<16>(lds, SI_R1A, LSA, 1, 64, SI_R0, LSA, 128, 128, 0, SI_R0, 144);
-            si_pw<2, 2, 1, true, true, false>(fa, sw, bb, am, lds, lds, SI_R0, SI_R1B, LSA, 128, 8);
-            si_guards(lds, SI_R1B, 8, LSA, 128);
-            for (int i = tid; i < 8 * 8 * 5 + 8; i += SI_T) {
+            const float am = si_quant<16>(lds, SF_R1A, LSA, 1, 64, SF_R0, LSA, 128, 128, 0, SF_R0, 144);
+            si_pw<2, 2, 1, true, true, false>(fa, sw, bb, am, lds, lds, SF_R0, SF_R1B, LSA, 128, 8);
+            sf_guards(lds, SF_R1B, 8, LSA, 128);
+            for (int i = tid; i < 8 * 8 * 5 + 8; i += SF_T) {
                 int d = i;
                 if (i < 320) {
                     const int ci = i / 40, r = i - ci * 40, co = r / 5, k = r - co * 5;
                     d = (((co >> 2) * 8 + ci) * 5 + k) * 4 + (co & 3);
                 }
-                lds[SI_DWB + d] = blobf[A.o[O_LAST] + i];
+                lds[SF_DWB + d] = blobf[A.o[O_LAST] + i];
             }
             request_x(n + gridDim.x);
             SI_SYNC();
             float* yg = A.y + (size_t)n * 8 * 257;
             {
-                const int t_ = si_tid();
+                const int t_ = sf_tid();
                 const int j = t_ & 127, cg = __builtin_amdgcn_readfirstlane(t_ >> 7);
-                const float* in = lds + SI_R1B + 4 + j;
-                const f32x4* W4 = (const f32x4*)(lds + SI_DWB) + cg * 40;
-                f32x4 a0 = *(const f32x4*)(lds + SI_DWB + 320 + 4 * cg), a1 = a0;
+                const float* in = lds + SF_R1B + 4 + j;
+                const f32x4* W4 = (const f32x4*)(lds + SF_DWB) + cg * 40;
+                f32x4 a0 = *(const f32x4*)(lds + SF_DWB + 320 + 4 * cg), a1 = a0;
 #pragma unroll
                 for (int ci = 0; ci < 8; ++ci) {
                     const float xm = in[ci * LSA - 1], x0 = in[ci * LSA], xp = in[ci * LSA + 1];
@@ -603,10 +511,10 @@ __global__ __launch_bounds__(SI_T, 1) void stream_fwd_i8_kernel(const SiArgs A) 
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) { yb[c4 * 257] = a0[c4]; yb[c4 * 257 + 1] = a1[c4]; }
                 if (t_ < 8) {
-                    float v = lds[SI_DWB + 320 + t_];
+                    float v = lds[SF_DWB + 320 + t_];
 #pragma unroll
                     for (int ci = 0; ci < 8; ++ci)
-                        v = fmaf(lds[SI_DWB + (((t_ >> 2) * 8 + ci) * 5 + 3) * 4 + (t_ & 3)], lds[SI_R1B + ci * LSA + 4 + 127], v);
+                        v = fmaf(lds[SF_DWB + (((t_ >> 2) * 8 + ci) * 5 + 3) * 4 + (t_ & 3)], lds[SF_R1B + ci * LSA + 4 + 127], v);
                     yg[t_ * 257 + 256] = v;
                 }
             }
@@ -656,10 +564,10 @@ extern "C" int trunet_stream_fwd_i8(const float* x, float* y, const void* blob, 
     a.x = x; a.y = y; a.blob = (const uint32_t*)blob; a.scratch = scratch; a.words = blob_bytes >> 2; a.N = N; a.Cin = Cin;
     for (int k = 0; k < SI_NOFF; ++k) a.o[k] = h_offsets[k];
     const int grid = trunet_stream_fwd_grid(N);
-    const size_t ldsb = (size_t)SI_ARENA * sizeof(float);
+    const size_t ldsb = (size_t)SF_ARENA * sizeof(float);
     if (hipFuncSetAttribute((const void*)stream_fwd_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb) != hipSuccess)
         return TRUNET_ELAUNCH;
-    hipLaunchKernelGGL(stream_fwd_i8_kernel, dim3(grid), dim3(SI_T), ldsb, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stream_fwd_i8_kernel, dim3(grid), dim3(SF_T), ldsb, (hipStream_t)stream, a);
     return trunet_launch_status();
 }
 

@@ -185,7 +185,7 @@ def _frag_tiles16_x3(Wm, bias):
     return np.concatenate(out)
 
 
-# matrix sections of the folded image: index -> (rows, K, 32- or 16-row tiles, layer group bit of stream_fwd_x3.hip's SFX_MASK)
+# matrix sections of the folded image: index -> (rows, K, 32- or 16-row tiles, layer group bit of stream_fwd.hip's SFX_MASK)
 _X3_SECTIONS = {1: (128, 64, 32, 1), 2: (128, 128, 32, 1), 3: (128, 128, 32, 1), 4: (128, 128, 32, 1), 5: (128, 128, 32, 1),
                 11: (384, 128, 16, 16), 13: (64, 128, 16, 16), 14: (64, 64, 16, 16),
                 15: (64, 192, 16, 2), 16: (64, 192, 16, 2), 17: (64, 192, 16, 2), 18: (64, 192, 16, 2), 19: (8, 128, 16, 16),
