@@ -101,7 +101,7 @@ int trunet_conv_gemm(const trunet_gemm_args* h_args, void* stream);
  * the fp32-MFMA kernels', tests/test_gemm_x3_gpu.py) at 6/16 of the fp32-MFMA time.  trunet_gemm_x3_enable(mask) selects
  * where (returns the previous mask; -1 only queries; environment TRUNET_GEMM_X3 = 0..3 sets the initial value):
  *   TRUNET_X3_BWD  (default ON)  the fused backward kernels trunet_pw_bwd (pw_bwd.hip) and trunet_convt_bwd
- *                  (convt_bwd_x3.hip).  Backward is a linear map of the saved forward state: the forward pass, the loss and
+ *                  (convt_bwd.hip).  Backward is a linear map of the saved forward state: the forward pass, the loss and
  *                  the loss gradient stay bit for bit those of the fp32-MFMA path, the parameter gradients move at the 1e-7
  *                  level, and every parity gate of the fp32 path holds unchanged.
  *   TRUNET_X3_GEMM (default OFF) the launches of trunet_conv_gemm without a tensor-operand epilogue (no TRUNET_EPI_MASK /

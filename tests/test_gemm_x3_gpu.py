@@ -136,7 +136,7 @@ def test_x3_gru_projection_three_row_blocks():
                                     ("dsc_k3s2", 300), ("last_tr", 420)])
 def test_x3_fused_backward_kernels_vs_their_fp32_mfma_instances(name, N):
     """The fused backward kernels with both GEMMs on the bf16 MFMA through the three-term split (TRUNET_X3_BWD, the default
-    since round 4) -- convt_bwd_x3_kernel<K, S> (ConvTranspose1d(64 -> 64) + BatchNorm) and pw_bwd_kernel<AK, SEC, KSPLIT, true>
+    since round 4) -- convt_bwd_kernel<K, S, true> (ConvTranspose1d(64 -> 64) + BatchNorm) and pw_bwd_kernel<AK, SEC, KSPLIT, true>
     (Conv1d(k = 1) + BatchNorm: <64, ., KSPLIT> dsc_k3s1, <64> dsc_k5s2 / dsc_k3s2, <32, SEC> the decoder blocks, <32>
     first_tr, <16> last_tr) -- against their fp32-MFMA instances on the SAME recorded forward state and cotangent: the
     backward is linear given the state and both multiply the same fp32 numbers, so every parameter and input gradient of the

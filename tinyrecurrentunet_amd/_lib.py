@@ -261,7 +261,7 @@ _MFMA_KINDS = {"fp32": 0, "bf16x3-bwd": X3_BWD, "bf16x3-fwd": X3_GEMM, "bf16x3":
 def set_fp32_mfma(kind):
     """Which matrix instruction the fp32 GEMM kernels multiply on (storage, accumulation and results are fp32 in every case).
     "fp32": v_mfma_f32_32x32x2_f32 everywhere.  "bf16x3-bwd" (the default since round 4): the fused backward kernels
-    (pw_bwd.hip, convt_bwd_x3.hip) split their fp32 operands into three bf16 terms and multiply on the bf16 MFMA -- backward
+    (pw_bwd.hip, convt_bwd.hip) split their fp32 operands into three bf16 terms and multiply on the bf16 MFMA -- backward
     is linear in the saved forward state, so the forward pass, the loss and the loss gradient are bit for bit those of
     "fp32" and the parameter gradients move at the 1e-7 level.  "bf16x3" (opt-in): the forward implicit GEMMs as well
     (gemm_x3.hip): same accuracy against float64, different rounding pattern of the network output.

@@ -1,5 +1,5 @@
-// Fused backward of a ConvTranspose1d(64 -> 64, k = K, stride S, padding S/2) + BatchNorm layer (autograd of
-// /root/reference/network.py:67,86 with the BatchNorm of :72,91 behind it and the BatchNorm+ReLU of :65-66,84-85 in front):
+// Fused backward of a ConvTranspose1d(64 -> 64, k = K, stride S, padding S/2) + BatchNorm layer (autograd of the reference's
+// network.py:67,86 with the BatchNorm of :72,91 behind it and the BatchNorm+ReLU of :65-66,84-85 in front):
 //   z[co][p][n] = b[co] + sum_{ci,k} W[ci][co][k] a[ci][q][n],  p = q S - pad + k,   a = max(sc zs + sh, 0)
 // ONE pass over (dy, z, zs) produces
 //   dz        = ca dy + cb z + cc                                   (BatchNorm backward of z: in LDS only)
@@ -22,7 +22,23 @@
 //   waves 4-7  data gradient: wave (ci tile, co half) keeps W^T fragments of its 32 co rows for all taps in registers;
 //              the two co halves of a ci tile are combined through LDS, and the co-half-0 wave runs the epilogue (ReLU mask,
 //              store, statistics) from registers after the barrier, in the shadow of the next step.
-#include "common.hpp"
+//
+// ONE kernel source, two operand paths (template parameter X3).  X3 = false runs both GEMMs on the fp32 MFMA
+// (v_mfma_f32_32x32x2_f32, two workgroups per CU).  X3 = true, the default of the training step (trunet_gemm_x3_enable /
+// TRUNET_GEMM_X3, gemm_x3.hip), runs them on the bf16 MFMA through the three-term operand split of x3_common.hpp (round 4;
+// fp32-grade result, one workgroup per CU).  Decomposition, rings, DMA schedule, prologue arithmetic and epilogue are the
+// same text; what differs is how a staged fp32 fragment reaches the matrix pipe:
+//   weight gradient (waves 0-3): per 16 frames the source row's 8 values of a lane (two swizzled 16-byte pieces) get
+//       BatchNorm+ReLU and are split ONCE, every valid tap's dz row fragment is split, 6 v_mfma_f32_32x32x16_bf16 per tap;
+//   data gradient (waves 4-7): W^T of the wave's (ci tile, co half) for all taps sits in registers as three bf16 fragment
+//       planes (split once per kernel), per tap and 16 co rows the lane's 8 dz values (8 ds_read_b32) are split, 6 MFMAs.
+// Here a staged fragment feeds ONE 32-row tile per wave, so the split is not amortised (about 7 vector instructions per
+// MFMA: the waves are vector-bound) -- and still well ahead of the fp32 MFMA: 6 x 33 matrix cycles + ~45 x 4 vector cycles
+// per (32 x 32 x 16) against 8 x 64.  The fp32-MFMA instance was the most matrix-bound kernel of the step (matrix pipe
+// 62-65 % busy, HBM at 0.25 of its peak).
+#include <type_traits>
+#include "dma_common.hpp"
+#include "x3_common.hpp"
 
 namespace {
 
@@ -30,43 +46,59 @@ constexpr int CT_F = 32;            // frames per tile
 constexpr int CT_C = 64;            // channels (both sides)
 constexpr int CT_SET = CT_C * CT_F; // floats per row set (8 KB)
 constexpr int CT_GRID = TRUNET_NUM_CU;
+constexpr int CT_LO = CT_C * 16;    // floats per row set of the lo-plane ring (8 bytes per 4 frames)
 
-typedef __attribute__((address_space(3))) void* ct_lds_ptr_t;
+// (X3; round 4, as in pw_bwd.hip) dz is split ONCE, by the prologue pass that computes it: the dz ring keeps [hi | mid] of a
+// piece's 4 frames in the piece's own 16 bytes, a second ring of 4 KB slots the lo plane.  The weight-gradient B fragments
+// (K = frames) are then 8-byte reads, the data-gradient B fragments (K = dz rows) transposing reads (ds_read_b64_tr_b16),
+// neither with vector work; only the source rows are still split by the wave that consumes them.  Needs (K + 2 S) x 4 KB
+// more LDS: k3 s1 fits (126 KB); k3 s2 (166 KB) and k5 s2 (190 KB) do not and keep the consumer-side split.
+template <int K, int S>
+constexpr bool ct_dzp() { return K == 3 && S == 1; }
 
-__device__ __forceinline__ void ct_wait_vmcnt(int n) {
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15)
-        W_(16) W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24) W_(25) W_(26) W_(27) W_(28) W_(29) W_(30) W_(31)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
+// float offset of the 8 lo bytes of logical piece `pc` of row `r` inside a lo-ring slot (same swizzle as the row set)
+__device__ __forceinline__ int ct_lo_off(int r, int pc) { return r * 16 + 2 * (pc ^ ((r >> 1) & 7)); }
 
-// swizzled float offset of 16-byte piece `pc` (0..7) of row `r` inside a row set
-__device__ __forceinline__ int ct_off(int r, int pc) { return r * CT_F + 4 * (pc ^ ((r >> 1) & 7)); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ct_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
 __device__ __forceinline__ void ct_bstore(__amdgpu_buffer_rsrc_t r, int voff, int soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, voff, soff, 0);
 }
-__device__ __forceinline__ int ct_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-template <int K, int S>
-__global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bwd_args a) {
-    constexpr int PAD = S / 2;
-    constexpr int RDZ = K + 2 * S;      // dz ring: window + the rows of the next two steps
-    constexpr int ZS = 2 * S;           // z staging slots
-    constexpr int RS = 4;               // source ring: q (+ epilogue of q - 1), q + 1, q + 2
+// ring depths and the carve-up of the dynamic LDS (float offsets), for the kernel and its launcher
+template <int K, int S, bool X3>
+struct CtLds {
+    static constexpr bool DZP = X3 && ct_dzp<K, S>();
+    static constexpr int RDZ = K + 2 * S;       // dz ring: window + the rows of the next two steps
+    static constexpr int ZS = 2 * S;            // z staging slots
+    static constexpr int RS = 4;                // source ring: q (+ epilogue of q - 1), q + 1, q + 2
+    static constexpr int DZ = 0;                                // [RDZ][64][32]
+    static constexpr int ZST = DZ + RDZ * CT_SET;               // [ZS][64][32]
+    static constexpr int SRC = ZST + ZS * CT_SET;               // [RS][64][32]
+    static constexpr int PART = SRC + RS * CT_SET;              // [2 parity][2 ci tiles][16][64]
+    static constexpr int LO = PART + 2 * 2 * 16 * 64;           // (DZP) [RDZ][64][16]: lo plane of the dz ring
+    static constexpr int COEF = LO + (DZP ? RDZ * CT_LO : 0);   // f32x4 [2][64]: (ca, cb, cc, 0) of dz, (sc, sh, mean, 0) of the source
+    static constexpr size_t BYTES = COEF * sizeof(float) + 2 * CT_C * sizeof(f32x4);
+    static_assert(BYTES <= 160 * 1024, "LDS");
+};
+
+// W^T fragments of a data-gradient wave (row ci = 32 cit + c) for all taps, in the form its MFMA takes them
+template <int K>
+struct CtWtF32 { float af[K][16]; };                    // af[k][kk] = W[ci][co = 32 chf + 2 kk + h][k]
+template <int K>
+struct CtWtX3 { u32x4 A0[K][2], A1[K][2], A2[K][2]; };  // planes of co = 32 chf + 16 ks + 8 h + j, j < 8, per tap and K-step ks
+
+template <int K, int S, bool X3>
+__global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet_convt_bwd_args a) {
+    using L = CtLds<K, S, X3>;
+    constexpr int PAD = S / 2, RDZ = L::RDZ, ZS = L::ZS, RS = L::RS;
+    constexpr bool DZP = L::DZP;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* DZ = smem;                               // [RDZ][64][32]
-    float* ZST = DZ + RDZ * CT_SET;                 // [ZS][64][32]
-    float* SRC = ZST + ZS * CT_SET;                 // [RS][64][32]
-    float* PART = SRC + RS * CT_SET;                // [2 parity][2 ci tiles][16][64]
-    f32x4* CA = (f32x4*)(PART + 2 * 2 * 16 * 64);   // [64] (ca, cb, cc, 0) of dz
-    f32x4* CB = CA + CT_C;                          // [64] (sc, sh, mean, 0) of the source
+    float* DZ = smem + L::DZ;
+    float* ZST = smem + L::ZST;
+    float* SRC = smem + L::SRC;
+    float* PART = smem + L::PART;
+    float* LO = smem + L::LO;
+    f32x4* CA = (f32x4*)(smem + L::COEF);
+    f32x4* CB = CA + CT_C;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -112,8 +144,8 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const size_t off = ((size_t)row_[i] * Lout + p) * NP + n0 + 4 * lc_[i];
-                    __builtin_amdgcn_global_load_lds(a.dy + off, (ct_lds_ptr_t)(dst + (wave + 4 * i) * 256), 16, 0, TRUNET_DMA_AUX);
-                    __builtin_amdgcn_global_load_lds(a.z + off, (ct_lds_ptr_t)(zst + (wave + 4 * i) * 256), 16, 0, TRUNET_DMA_AUX);
+                    __builtin_amdgcn_global_load_lds(a.dy + off, (lds_ptr_t)(dst + (wave + 4 * i) * 256), 16, 0, TRUNET_DMA_AUX);
+                    __builtin_amdgcn_global_load_lds(a.z + off, (lds_ptr_t)(zst + (wave + 4 * i) * 256), 16, 0, TRUNET_DMA_AUX);
                 }
                 n += 4;
             }
@@ -122,7 +154,7 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const size_t off = ((size_t)row_[i] * Lin + sq) * NP + n0 + 4 * lc_[i];
-                    __builtin_amdgcn_global_load_lds(a.src + off, (ct_lds_ptr_t)(sdst + (wave + 4 * i) * 256), 16, 0, TRUNET_DMA_AUX);
+                    __builtin_amdgcn_global_load_lds(a.src + off, (lds_ptr_t)(sdst + (wave + 4 * i) * 256), 16, 0, TRUNET_DMA_AUX);
                 }
                 n += 2;
             }
@@ -147,12 +179,24 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
                         s += v[e];
                     }
                     bsum[i] += s;
-                    *(f32x4*)(dst + o) = v;
+                    if constexpr (DZP) {
+                        unsigned h0, m0, l0, h1, m1, l1;
+                        ctx_split2(v[0], v[1], h0, m0, l0);
+                        ctx_split2(v[2], v[3], h1, m1, l1);
+                        *(u32x4*)(dst + o) = u32x4{h0, h1, m0, m1};
+                        *(u32x2*)(LO + (p % RDZ) * CT_LO + row_[i] * 16 + 2 * pc) = u32x2{l0, l1};
+                    } else {
+                        *(f32x4*)(dst + o) = v;
+                    }
                 }
             }
         };
         // dz rows first needed at step q >= 1: the S highest rows of its window
         auto new_lo = [&](int q) { return q * S - PAD + K - S; };
+
+        // K-steps of a position (the fp32 MFMA takes 8 frames, the six bf16 MFMAs 16) and the one that carries the
+        // prologue of the next position
+        constexpr int NQQ = X3 ? CT_F / 16 : CT_F / 8, QQ_PRO = X3 ? 0 : 1;
 
         for (int ch = c_begin; ch < c_end; ++ch) {
             const int n0 = ch * CT_F;
@@ -176,24 +220,60 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
                 const float* Ssrc = SRC + (q % RS) * CT_SET;
                 const int ra = cit * 32 + c, rb = cot * 32 + c;
 #pragma unroll
-                for (int qq = 0; qq < CT_F / 8; ++qq) {
-                    f32x4 av = *(const f32x4*)(Ssrc + ct_off(ra, 2 * qq + h));
+                for (int qq = 0; qq < NQQ; ++qq) {
+                    if constexpr (X3) {
+                        // this lane's 8 frames of the K-step: 16 qq + 8 h .. + 7 = pieces 4 qq + 2 h, 4 qq + 2 h + 1 of its row
+                        f32x4 av0 = *(const f32x4*)(Ssrc + swz_off(ra, 4 * qq + 2 * h));
+                        f32x4 av1 = *(const f32x4*)(Ssrc + swz_off(ra, 4 * qq + 2 * h + 1));
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) av[e] = fmaxf(fmaf(av[e], sc_a, sh_a), 0.f);
+                        for (int e = 0; e < 4; ++e) {
+                            av0[e] = fmaxf(fmaf(av0[e], sc_a, sh_a), 0.f);
+                            av1[e] = fmaxf(fmaf(av1[e], sc_a, sh_a), 0.f);
+                        }
+                        u32x4 a0, a1, a2;
+                        ctx_split8(av0, av1, a0, a1, a2);
 #pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        const int p = q * S - PAD + k;
-                        if (p >= 0 && p < Lout) {
-                            const f32x4 bv = *(const f32x4*)(DZ + (p % RDZ) * CT_SET + ct_off(rb, 2 * qq + h));
+                        for (int k = 0; k < K; ++k) {
+                            const int p = q * S - PAD + k;
+                            if (p >= 0 && p < Lout) {
+                                const float* Dp = DZ + (p % RDZ) * CT_SET;
+                                u32x4 b0, b1, b2;
+                                if constexpr (DZP) {
+                                    const float* Lp = LO + (p % RDZ) * CT_LO;
+                                    const u32x4 q0 = *(const u32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h));
+                                    const u32x4 q1 = *(const u32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h + 1));
+                                    const u32x2 l0 = *(const u32x2*)(Lp + ct_lo_off(rb, 4 * qq + 2 * h));
+                                    const u32x2 l1 = *(const u32x2*)(Lp + ct_lo_off(rb, 4 * qq + 2 * h + 1));
+                                    b0 = u32x4{q0[0], q0[1], q1[0], q1[1]};
+                                    b1 = u32x4{q0[2], q0[3], q1[2], q1[3]};
+                                    b2 = u32x4{l0[0], l0[1], l1[0], l1[1]};
+                                } else {
+                                    const f32x4 bv0 = *(const f32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h));
+                                    const f32x4 bv1 = *(const f32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h + 1));
+                                    ctx_split8(bv0, bv1, b0, b1, b2);
+                                }
+                                CTX_MF6(acc[k], a0, a1, a2, b0, b1, b2);
+                            }
+                        }
+                    } else {
+                        f32x4 av = *(const f32x4*)(Ssrc + swz_off(ra, 2 * qq + h));
 #pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[k], 0, 0, 0);
+                        for (int e = 0; e < 4; ++e) av[e] = fmaxf(fmaf(av[e], sc_a, sh_a), 0.f);
+#pragma unroll
+                        for (int k = 0; k < K; ++k) {
+                            const int p = q * S - PAD + k;
+                            if (p >= 0 && p < Lout) {
+                                const f32x4 bv = *(const f32x4*)(DZ + (p % RDZ) * CT_SET + swz_off(rb, 2 * qq + h));
+#pragma unroll
+                                for (int j = 0; j < 4; ++j)
+                                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[k], 0, 0, 0);
+                            }
                         }
                     }
-                    if (qq == 1 && q >= 1) {
+                    if (qq == QQ_PRO && q >= 1) {
                         // outstanding: rows of step q + 1 (older) and of step q + 2 (the newest n_last): transform the
                         // rows of step q + 1 in the shadow of this step's MFMAs
-                        ct_wait_vmcnt(n_last);
+                        wait_vmcnt_exact<31>(n_last);
                         prologue(new_lo(q + 1), new_lo(q + 1) + S, n0);
                     }
                 }
@@ -231,14 +311,28 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
         // =============================================================== data gradient
         const int jj = wave - 4;
         const int cit = jj & 1, chf = jj >> 1;           // ci tile, co half
-        // W^T fragments: A[i = ci][k = co] per tap: af[k][kk] = W[ci = 32 cit + (lane & 31)][co = 32 chf + 2 kk + h][k]
-        float af[K][16];
-        {
+        const int trr = 8 * (lane >> 5) + ((lane & 15) >> 2), trp = 4 * ((lane >> 4) & 1) + (lane & 3);     // (DZP) transposing reads
+        std::conditional_t<X3, CtWtX3<K>, CtWtF32<K>> wt;
+        if constexpr (X3) {
+            const float* wp = a.W + ((size_t)(cit * 32 + c) * CT_C + chf * 32 + 8 * h) * K;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    f32x4 w0, w1;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        w0[j] = wp[(size_t)(16 * ks + j) * K + k];
+                        w1[j] = wp[(size_t)(16 * ks + 4 + j) * K + k];
+                    }
+                    ctx_split8(w0, w1, wt.A0[k][ks], wt.A1[k][ks], wt.A2[k][ks]);
+                }
+        } else {
             const float* wp = a.W + ((size_t)(cit * 32 + c) * CT_C + chf * 32 + h) * K;
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk)
 #pragma unroll
-                for (int k = 0; k < K; ++k) af[k][kk] = wp[(size_t)(2 * kk) * K + k];
+                for (int k = 0; k < K; ++k) wt.af[k][kk] = wp[(size_t)(2 * kk) * K + k];
         }
         float st1[16], st2[16];
 #pragma unroll
@@ -252,7 +346,7 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
             // val = own half + the other co half (through LDS), ReLU mask from the raw source row set, store, statistics
             const float* P = PART + ((q & 1) * 2 + cit) * 16 * 64 + lane;
             const float* Ssrc = SRC + (q % RS) * CT_SET;
-            const __amdgpu_buffer_rsrc_t ro = ct_rsrc(a.dsrc + (size_t)(32 * cit) * dstride + (size_t)q * NP);
+            const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(a.dsrc + (size_t)(32 * cit) * dstride + (size_t)q * NP);
             const bool fin = n0 + c < a.N;
             const int nb = n0 * (int)sizeof(float);
 #pragma unroll
@@ -271,7 +365,7 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
         };
 
         for (int ch = c_begin; ch < c_end; ++ch) {
-            const int n0 = ct_uniform(ch * CT_F);
+            const int n0 = wave_uniform(ch * CT_F);
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();                // step 0 staged
             asm volatile("" ::: "memory");
@@ -281,13 +375,49 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const int p = q * S - PAD + k;
-                    if (p >= 0 && p < Lout) {
+                    if (p < 0 || p >= Lout) continue;
+                    // B fragment: this lane's frame c of the dz rows of the wave's co half; row r keeps its 16-byte pieces
+                    // XOR-swizzled by (r >> 1) & 7
+                    if constexpr (DZP) {
+                        // K-step ks: lane (G = lane >> 4, i = lane & 15) fetches the 4 frames of logical piece 4 (G & 1) + (i & 3) of row
+                        // 32 chf + 16 ks + 8 h + 4 t + (i >> 2) and receives frame c of the rows 8 h + 4 t .. + 3 (t = 0, 1)
+                        const float* Dq = DZ + (p % RDZ) * CT_SET;
+                        const float* Lq = LO + (p % RDZ) * CT_LO;
+#pragma unroll
+                        for (int ks = 0; ks < 2; ++ks) {
+                            const int r0 = chf * 32 + 16 * ks + trr;
+                            const u32x2 h0 = lds_tr16(Dq + swz_off(r0, trp)), h1 = lds_tr16(Dq + swz_off(r0 + 4, trp));
+                            const u32x2 m0 = lds_tr16(Dq + swz_off(r0, trp) + 2), m1 = lds_tr16(Dq + swz_off(r0 + 4, trp) + 2);
+                            const u32x2 l0 = lds_tr16(Lq + ct_lo_off(r0, trp)), l1 = lds_tr16(Lq + ct_lo_off(r0 + 4, trp));
+                            const u32x4 b0 = {h0[0], h0[1], h1[0], h1[1]}, b1 = {m0[0], m0[1], m1[0], m1[1]},
+                                        b2 = {l0[0], l0[1], l1[0], l1[1]};
+                            CTX_MF6(dacc, wt.A0[k][ks], wt.A1[k][ks], wt.A2[k][ks], b0, b1, b2);
+                        }
+                    } else if constexpr (X3) {
+                        // K-step ks: dz rows 32 chf + 16 ks + 8 h + j (j < 8), swizzle term (4 h + (j >> 1)) & 7 (32 chf + 16 ks
+                        // is a multiple of 16)
+                        const float* Sb = DZ + (p % RDZ) * CT_SET + (chf * 32 + 8 * h) * CT_F + (c & 3);
+                        const int cpc = c >> 2;
+#pragma unroll
+                        for (int ks = 0; ks < 2; ++ks) {
+                            f32x4 x0, x1;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                x0[j] = Sb[(16 * ks + j) * CT_F + 4 * (cpc ^ ((4 * h + (j >> 1)) & 7))];
+                                x1[j] = Sb[(16 * ks + 4 + j) * CT_F + 4 * (cpc ^ ((4 * h + 2 + (j >> 1)) & 7))];
+                            }
+                            u32x4 b0, b1, b2;
+                            ctx_split8(x0, x1, b0, b1, b2);
+                            CTX_MF6(dacc, wt.A0[k][ks], wt.A1[k][ks], wt.A2[k][ks], b0, b1, b2);
+                        }
+                    } else {
+                        // K-step kk: dz rows 32 chf + 2 kk + h
                         const float* Sb = DZ + (p % RDZ) * CT_SET + (chf * 32 + h) * CT_F + (c & 3);
                         const int cpc = c >> 2;
 #pragma unroll
                         for (int kk = 0; kk < 16; ++kk) {
                             const float b = Sb[kk * (2 * CT_F) + 4 * (cpc ^ (kk & 7))];
-                            dacc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[k][kk], b, dacc, 0, 0, 0);
+                            dacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wt.af[k][kk], b, dacc, 0, 0, 0);
                         }
                     }
                 }
@@ -321,25 +451,23 @@ __global__ __launch_bounds__(512, 2) void convt_bwd_kernel(const trunet_convt_bw
     }
 }
 
-template <int K, int S>
+template <int K, int S, bool X3>
 int ct_launch(const trunet_convt_bwd_args* h, hipStream_t st) {
-    constexpr int RDZ = K + 2 * S, ZS = 2 * S, RS = 4;
-    const size_t lds = ((size_t)(RDZ + ZS + RS) * CT_SET + 2 * 2 * 16 * 64) * sizeof(float) + 2 * CT_C * sizeof(f32x4);
-    auto kern = convt_bwd_kernel<K, S>;
+    constexpr size_t lds = CtLds<K, S, X3>::BYTES;
+    auto kern = convt_bwd_kernel<K, S, X3>;
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return TRUNET_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(CT_GRID), dim3(512), lds, st, *h);
     return trunet_launch_status();
 }
+template <int K, int S>
+int ct_launch(const trunet_convt_bwd_args* h, hipStream_t st, bool x3) {
+    return x3 ? ct_launch<K, S, true>(h, st) : ct_launch<K, S, false>(h, st);
+}
 
 }  // namespace
 
 extern "C" int trunet_convt_bwd_nparts(void) { return CT_GRID; }
-
-// convt_bwd_x3.hip: the same kernel with both GEMMs on the bf16 MFMA (three-term operand split, fp32-grade result);
-// taken when the split path is on (trunet_gemm_x3_enable / TRUNET_GEMM_X3, gemm_x3.hip)
-int trunet_launch_convt_bwd_x3(const trunet_convt_bwd_args* h, hipStream_t st);
-extern "C" int trunet_gemm_x3_enable(int on);
 
 extern "C" int trunet_convt_bwd(const trunet_convt_bwd_args* h, void* stream) {
     if (!h || !h->dy || !h->z || !h->ca || !h->cb || !h->cc || !h->src || !h->s_scale || !h->s_shift || !h->s_mean ||
@@ -352,9 +480,10 @@ extern "C" int trunet_convt_bwd(const trunet_convt_bwd_args* h, void* stream) {
     // 32-bit byte offsets of the buffer stores: 36 channel rows of the gradient tensor below 2 GiB
     if ((size_t)h->Lin * h->NP * sizeof(float) * 36 >= ((size_t)1 << 31)) return TRUNET_ENOTSUP;
     hipStream_t st = (hipStream_t)stream;
-    if (trunet_gemm_x3_enable(-1) & (TRUNET_X3_BWD | 8)) return trunet_launch_convt_bwd_x3(h, st);
-    if (h->K == 3 && h->S == 1) return ct_launch<3, 1>(h, st);
-    if (h->K == 3 && h->S == 2) return ct_launch<3, 2>(h, st);
-    if (h->K == 5 && h->S == 2) return ct_launch<5, 2>(h, st);
+    // the split path when it is on for the fused backward kernels, or for this kernel alone (diagnostic mode 8)
+    const bool x3 = (trunet_gemm_x3_enable(-1) & (TRUNET_X3_BWD | 8)) != 0;
+    if (h->K == 3 && h->S == 1) return ct_launch<3, 1>(h, st, x3);
+    if (h->K == 3 && h->S == 2) return ct_launch<3, 2>(h, st, x3);
+    if (h->K == 5 && h->S == 2) return ct_launch<5, 2>(h, st, x3);
     return TRUNET_ENOTSUP;
 }

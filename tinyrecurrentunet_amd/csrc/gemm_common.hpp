@@ -1,7 +1,7 @@
 // Device helpers of the implicit-GEMM kernels (gemm_conv.hip): segment addressing, the flattened
-// stream of K-chunks a persistent workgroup walks, counted vmcnt waits, LDS address-space pointer.
+// stream of K-chunks a persistent workgroup walks, the vmcnt wait of its ring (counts rounded down to a multiple of 4).
 #pragma once
-#include "common.hpp"
+#include "dma_common.hpp"
 
 namespace {
 
@@ -115,7 +115,5 @@ __device__ __forceinline__ void wait_vmcnt(int n) {   // n = LDS-DMA instruction
         default: asm volatile("s_waitcnt vmcnt(48)" ::: "memory"); break;
     }
 }
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 }  // namespace

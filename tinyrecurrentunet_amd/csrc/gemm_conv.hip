@@ -687,23 +687,9 @@ extern "C" int trunet_conv_gemm(const trunet_gemm_args* h, void* stream) {
 namespace {
 
 constexpr int WFC = 32;         // frames per tile
+static_assert(WFC == 32, "swz_off (dma_common.hpp) is the piece offset of 32-frame rows");
 constexpr int MAXT = 3;         // accumulator tiles per wave (8 waves)
 constexpr int WGRAD_GRID = TRUNET_NUM_CU;
-
-__device__ __forceinline__ void wait_vmcnt_any(int n) {
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15)
-        W_(16) W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24) W_(25) W_(26) W_(27) W_(28) W_(29) W_(30) W_(31)
-        W_(32) W_(33) W_(34) W_(35) W_(36) W_(37) W_(38) W_(39) W_(40) W_(41) W_(42) W_(43) W_(44) W_(45) W_(46) W_(47)
-        W_(48) W_(49) W_(50) W_(51) W_(52) W_(53) W_(54) W_(55) W_(56) W_(57) W_(58) W_(59) W_(60)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
-// swizzled float offset of 16-byte piece `pc` (0..7) of row `r` inside a slot
-__device__ __forceinline__ int wg_off(int r, int pc) { return r * WFC + 4 * (pc ^ ((r >> 1) & 7)); }
 
 template <bool TWO>
 __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const trunet_wgrad_args a, const int NB, const int nvmax,
@@ -937,7 +923,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const trunet_wgrad_a
 
             // ---- pipeline over tiles [t0, t1): NB tiles in flight, first one transformed
             for (int d = 0; d < NB; ++d) issue_dma(min(t0 + d, t1 - 1), d);
-            wait_vmcnt_any((NB - 1) * LPW);
+            wait_vmcnt_exact<60>((NB - 1) * LPW);
             transform(t0, 0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // a raw s_barrier does not wait for the LDS writes above
             __builtin_amdgcn_s_barrier();
@@ -945,7 +931,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const trunet_wgrad_a
             int slot = 0;
             for (int t = t0; t < t1; ++t) {
                 if (t + 1 < t1) {
-                    wait_vmcnt_any((NB - 2) * LPW);
+                    wait_vmcnt_exact<60>((NB - 2) * LPW);
                     transform(t + 1, (slot + 1 == NB) ? 0 : slot + 1);
                 }
                 const float* S = R_lds + (size_t)slot * SLOT;
@@ -960,8 +946,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const trunet_wgrad_a
                             const int rb = sb + t_ct[i] * 32 + c;
 #pragma unroll
                             for (int q = 0; q < WFC / 8; ++q) {
-                                const f32x4 av = *(const f32x4*)(S + wg_off(ra, 2 * q + h));
-                                const f32x4 bv = *(const f32x4*)(S + wg_off(rb, 2 * q + h));
+                                const f32x4 av = *(const f32x4*)(S + swz_off(ra, 2 * q + h));
+                                const f32x4 bv = *(const f32x4*)(S + swz_off(rb, 2 * q + h));
 #pragma unroll
                                 for (int j = 0; j < 4; ++j)
                                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[i], 0, 0, 0);

@@ -21,26 +21,13 @@
 // Scope: launches without a tensor-operand epilogue (no ReLU mask / accumulate: the forward pass), one-tensor prologue
 // (BN+ReLU or none), M = 64 or a multiple of 128, frame count padded to 256.  Everything else stays on conv_gemm_kernel.
 #include <cstdlib>
-#include "common.hpp"
-
-#include "bf16_common.hpp"
 #include "gemm_common.hpp"
+#include "x3_common.hpp"
 
 namespace {
 
 constexpr int X3_KC = 16;          // K rows per chunk = one MFMA K-step
 constexpr int X3_FT = 256;         // frames per tile (8 waves x 32)
-
-// three-way split of two floats into bf16 terms, packed (element 0 in the low half): x = hi + mid + lo with every term
-// rounded to NEAREST (v_cvt_pk_bf16_f32), so the residues are signed and zero-mean: hi carries 8 significand bits, x - hi
-// is exact in fp32, mid its leading 8 bits, lo the rest (exact up to one unit in the 25th bit).  Same instruction count
-// as a truncating split (and / sub), without its bias towards zero in the dropped cross terms.
-__device__ __forceinline__ void x3_split2(float x0, float x1, unsigned& hi, unsigned& mid, unsigned& lo) {
-    hi = bf_pack(x0, x1);
-    const float r0 = x0 - bf_lo(hi), r1 = x1 - bf_hi(hi);
-    mid = bf_pack(r0, r1);
-    lo = bf_pack(r0 - bf_lo(mid), r1 - bf_hi(mid));
-}
 
 // counted wait for the LDS-DMA ring (2 instructions per wave and chunk); the large counts are used while the stores of a
 // tile's epilogue (16 NRT per lane, younger than the DMA being waited for) may still be in flight
@@ -118,7 +105,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_x3_kernel(const trunet_gemm_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned u0, u1, u2;
-                x3_split2(v[2 * j], v[2 * j + 1], u0, u1, u2);
+                ctx_split2(v[2 * j], v[2 * j + 1], u0, u1, u2);
                 p0[j] = u0; p1[j] = u1; p2[j] = u2;
             }
             u32x4* dst = A3 + ((size_t)(ch * NRT + rt) * 3) * 64 + ln;
@@ -195,7 +182,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_x3_kernel(const trunet_gemm_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned u0, u1, u2;
-                x3_split2(x[2 * j], x[2 * j + 1], u0, u1, u2);
+                ctx_split2(x[2 * j], x[2 * j + 1], u0, u1, u2);
                 q0[j] = u0; q1[j] = u1; q2[j] = u2;
             }
         };
@@ -300,9 +287,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_x3_kernel(const trunet_gemm_
 #pragma unroll
             for (int t = 0; t < NRT; ++t) {
                 float s1[16], s2[16];
-                const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-                    a.out + ((size_t)(mblk * MB + 32 * t + a.m_out_off) * a.out_L + tp + a.out_pos_off) * a.NP + tn0, 0,
-                    0x7fffffff, 0x00020000);
+                const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(
+                    a.out + ((size_t)(mblk * MB + 32 * t + a.m_out_off) * a.out_L + tp + a.out_pos_off) * a.NP + tn0);
                 const bool fin = nn < a.N;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {

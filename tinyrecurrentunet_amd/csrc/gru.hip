@@ -9,7 +9,7 @@
 // torch gate order (r, z, n):  r = s(gi_r + W_hr h + b_hr), z = s(gi_z + W_hz h + b_hz),
 // n = tanh(gi_n + r * (W_hn h + b_hn)), h' = (1 - z) n + z h.
 #include <cstdlib>
-#include "common.hpp"
+#include "dma_common.hpp"
 
 // gi, the gates and the recurrence outputs are touched once per launch: non-temporal policy (same-box A/B: -0.15 ms per step)
 
@@ -290,12 +290,9 @@ namespace {
 constexpr int TH = 128;    // hidden units
 constexpr int TS = 32;     // sequences per workgroup
 
-// Global rows as buffer resource (SGPR descriptor of a uniform base) + uniform SGPR row offset + one per-lane VGPR offset:
+// Global rows as buffer resource (buffer_rsrc: SGPR descriptor of a uniform base) + uniform SGPR row offset + one per-lane VGPR offset:
 // sixteen rows x eight tensors of per-lane 64-bit addresses would not fit the register budget next to W_hh, and these
 // intrinsics are tracked by the compiler (waits, hazards), unlike hand-written asm loads.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tg_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
 __device__ __forceinline__ float tg_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
@@ -348,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void tgru_rec_fwd_kernel(const float* __res
         f32x16 acc[3];
         // kh = 0 waves seed the accumulators with gi (+ folded biases); gi_n stays aside, gh_n accumulates on b_hn alone
         if (kh == 0) {
-            const __amdgpu_buffer_rsrc_t rg = tg_rsrc(gi_all + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);   // uniform
+            const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(gi_all + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);   // uniform
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ro = ((r & 3) + 8 * (r >> 2)) * growb;
@@ -381,8 +378,8 @@ __global__ __launch_bounds__(512, 2) void tgru_rec_fwd_kernel(const float* __res
         __syncthreads();
         if (kh == 0) {
             float* hw = &hbuf[cur ^ 1][0][0];
-            const __amdgpu_buffer_rsrc_t rh = tg_rsrc(hs + (size_t)(32 * ut) * hrow + (size_t)(t + 1) * SP + s0);
-            const __amdgpu_buffer_rsrc_t rt = tg_rsrc(gates ? gates + (size_t)(32 * ut) * grow + (size_t)t * SP + s0 : hs);
+            const __amdgpu_buffer_rsrc_t rh = buffer_rsrc(hs + (size_t)(32 * ut) * hrow + (size_t)(t + 1) * SP + s0);
+            const __amdgpu_buffer_rsrc_t rt = buffer_rsrc(gates ? gates + (size_t)(32 * ut) * grow + (size_t)t * SP + s0 : hs);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ml = (r & 3) + 8 * (r >> 2);
@@ -446,11 +443,11 @@ __global__ __launch_bounds__(512, 2) void tgru_rec_bwd_kernel(const float* __res
     for (int t = T - 1; t >= 0; --t) {
         float dzd[16];                               // dh z: the direct path into h_{t-1}
         if (kh == 0) {
-            const __amdgpu_buffer_rsrc_t rdh = tg_rsrc(dhs + (size_t)(32 * ut) * hrow + (size_t)(t + 1) * SP + s0);   // uniform bases
-            const __amdgpu_buffer_rsrc_t rhp = tg_rsrc(hs + (size_t)(32 * ut) * hrow + (size_t)t * SP + s0);
-            const __amdgpu_buffer_rsrc_t rgt = tg_rsrc(gates + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);
-            const __amdgpu_buffer_rsrc_t rgi = tg_rsrc(dgi_all + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);
-            const __amdgpu_buffer_rsrc_t rgh = tg_rsrc(dgh_all + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);
+            const __amdgpu_buffer_rsrc_t rdh = buffer_rsrc(dhs + (size_t)(32 * ut) * hrow + (size_t)(t + 1) * SP + s0);   // uniform bases
+            const __amdgpu_buffer_rsrc_t rhp = buffer_rsrc(hs + (size_t)(32 * ut) * hrow + (size_t)t * SP + s0);
+            const __amdgpu_buffer_rsrc_t rgt = buffer_rsrc(gates + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);
+            const __amdgpu_buffer_rsrc_t rgi = buffer_rsrc(dgi_all + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);
+            const __amdgpu_buffer_rsrc_t rgh = buffer_rsrc(dgh_all + (size_t)(32 * ut) * grow + (size_t)t * SP + s0);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {            // four rows at a time: 24 loads in flight
                 float v[4][6];

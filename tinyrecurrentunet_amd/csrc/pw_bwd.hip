@@ -35,7 +35,7 @@
 // and was what bounded these kernels (matrix pipe 67 % busy at 0.55 of the HBM rate).
 #include <cstdlib>
 #include <type_traits>
-#include "common.hpp"
+#include "dma_common.hpp"
 #include "x3_common.hpp"
 
 #ifndef PWB_ABL      // diagnostic builds only (scripts/ubench_pwbwd.py): 1 no epilogue loads, 2 no epilogue stores,
@@ -63,12 +63,6 @@ __device__ __forceinline__ void pwb_split8(const f32x4 v0, const f32x4 v1, u32x4
 #define PWB_DZ_PLANES 2          // 1: dz only; 2: the source rows of the 128-row layers too (SRCP below)
 #endif
 
-typedef short pwb_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 pwb_tr16(const float* p) {
-    const pwb_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) pwb_s16x4*)p);
-    return __builtin_bit_cast(u32x2, v);
-}
-
 // (SRCP) the fp32 activation at float offset F of a slot (a source row's element: row * 32 + 4 * physical piece + frame & 3)
 // from its planes: hi / mid are halfwords (frame & 3) of the piece's first / second 8 bytes, lo of the second half of the same
 // piece MA rows further up (the z row); zrow_h = that distance in halfwords (negative).  Exact: hi + mid + lo in fp32.
@@ -81,6 +75,7 @@ __device__ __forceinline__ float pwb_act3(const float* S, int F, int c3, int zro
 }
 
 constexpr int WFC = 32;          // frames per tile
+static_assert(WFC == 32, "swz_off (dma_common.hpp) is the piece offset of 32-frame rows");
 constexpr int PMAXT = 4;         // weight-gradient accumulator tiles per wave (waves 0-3)
 constexpr int PSW = 6;           // source DMA row groups per loader wave (sum of channels <= 192)
 constexpr int PWB_GRID = TRUNET_NUM_CU;
@@ -92,22 +87,6 @@ struct PwbSched {
     int8_t rt2[4], period2[4], phase2[4], share2[4];     // secondary row tile (-1: none)
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void pwb_wait_vmcnt(int n) {
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15)
-        W_(16) W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24) W_(25) W_(26) W_(27) W_(28) W_(29) W_(30) W_(31)
-        W_(32) W_(33) W_(34) W_(35) W_(36) W_(37) W_(38) W_(39) W_(40) W_(41) W_(42) W_(43) W_(44) W_(45) W_(46) W_(47)
-        W_(48) W_(49) W_(50) W_(51) W_(52) W_(53) W_(54) W_(55) W_(56) W_(57) W_(58) W_(59) W_(60)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
-// swizzled float offset of 16-byte piece `pc` (0..7) of row `r` inside a slot
-__device__ __forceinline__ int pwb_off(int r, int pc) { return r * WFC + 4 * (pc ^ ((r >> 1) & 7)); }
 // The data-gradient epilogue reads its 32x32 tile of a source back from the slot in the MFMA C layout: lane (h, c), register
 // r <-> row rb + 4h + ml(r), ml = (r & 3) + 8 (r >> 2), frame c; rb is a multiple of 16, so the row's swizzle term is
 // ((4h + ml) >> 1) & 7 = 2h ^ kr with the compile-time kr = ((r & 3) >> 1) + 4 ((r >> 2) & 1): four per-lane offsets
@@ -125,14 +104,6 @@ __device__ __forceinline__ PSegPos pwb_seg_pos(const trunet_seg& sg, int p) {
     return r;
 }
 
-// Global rows as buffer resource (SGPR descriptor of a uniform base) + uniform SGPR row offset + one per-lane VGPR
-// offset: 64-bit per-row addresses for 16 rows x 3 tensors would not fit the register budget next to the W^T fragments,
-// and -- unlike hand-written asm loads -- the compiler tracks these, so a value is never copied or spilled before it has
-// arrived (an earlier inline-asm version produced a wrong 32x32 tile about once in a hundred launches under register
-// pressure).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pwb_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
 #ifndef TRUNET_PWB_DMA_AUX
 #define TRUNET_PWB_DMA_AUX TRUNET_DMA_AUX
 #endif
@@ -147,15 +118,15 @@ __device__ __forceinline__ void pwb_bstore(__amdgpu_buffer_rsrc_t r, int voff, i
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, voff, soff, TRUNET_PWB_AUX);
 }
 
-// wave-uniform values the compiler cannot prove uniform (they pass through per-wave role tables)
-__device__ __forceinline__ int pwb_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ size_t pwb_uniform(size_t v) {
+// wave-uniform values the compiler cannot prove uniform (they pass through per-wave role tables): the 64-bit forms of
+// wave_uniform(int) (dma_common.hpp)
+__device__ __forceinline__ size_t wave_uniform(size_t v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
     return ((size_t)hi << 32) | lo;
 }
 template <typename T>
-__device__ __forceinline__ T* pwb_uniform(T* p) { return (T*)pwb_uniform((size_t)p); }
+__device__ __forceinline__ T* wave_uniform(T* p) { return (T*)wave_uniform((size_t)p); }
 
 // one data-gradient row tile of a wave: what is fixed for the kernel ...
 struct DUnit {
@@ -436,7 +407,7 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
 
             // ---- run prologue: NB tiles in flight, first one transformed
             for (int d = 0; d < NB; ++d) issue_dma(min(t0 + d, t1 - 1), d);
-            pwb_wait_vmcnt((NB - 1) * LPW);
+            wait_vmcnt_exact<60>((NB - 1) * LPW);
             if (!(PWB_ABL & 4)) {
 #pragma unroll
                 for (int part = 0; part < PDW + PSW; ++part) tpart(part, t0, 0);
@@ -461,38 +432,38 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                         u32x4 a0, a1, a2;
                         if constexpr (DZP) {
                             // planes of the dz row: [hi | mid] in the row's own pieces, lo in the z row's
-                            const float* p0 = S + pwb_off(ra, 4 * qq + 2 * h);
-                            const float* p1 = S + pwb_off(ra, 4 * qq + 2 * h + 1);
+                            const float* p0 = S + swz_off(ra, 4 * qq + 2 * h);
+                            const float* p1 = S + swz_off(ra, 4 * qq + 2 * h + 1);
                             const u32x4 q0 = *(const u32x4*)p0, q1 = *(const u32x4*)p1;
                             const u32x2 l0 = *(const u32x2*)(p0 + MA * WFC), l1 = *(const u32x2*)(p1 + MA * WFC);
                             a0 = u32x4{q0[0], q0[1], q1[0], q1[1]};
                             a1 = u32x4{q0[2], q0[3], q1[2], q1[3]};
                             a2 = u32x4{l0[0], l0[1], l1[0], l1[1]};
                         } else {
-                            pwb_split8(*(const f32x4*)(S + pwb_off(ra, 4 * qq + 2 * h)),
-                                       *(const f32x4*)(S + pwb_off(ra, 4 * qq + 2 * h + 1)), a0, a1, a2);
+                            pwb_split8(*(const f32x4*)(S + swz_off(ra, 4 * qq + 2 * h)),
+                                       *(const f32x4*)(S + swz_off(ra, 4 * qq + 2 * h + 1)), a0, a1, a2);
                         }
 #pragma unroll
                         for (int i = 0; i < PMAXT; ++i) {
                             if (rb_run[i] >= 0 && !(PWB_ABL & 16)) {
                                 u32x4 b0, b1, b2;
                                 if constexpr (SRCP) {
-                                    const float* p0 = S + pwb_off(rb_run[i] + c, 4 * qq + 2 * h);
-                                    const float* p1 = S + pwb_off(rb_run[i] + c, 4 * qq + 2 * h + 1);
+                                    const float* p0 = S + swz_off(rb_run[i] + c, 4 * qq + 2 * h);
+                                    const float* p1 = S + swz_off(rb_run[i] + c, 4 * qq + 2 * h + 1);
                                     const u32x4 q0 = *(const u32x4*)p0, q1 = *(const u32x4*)p1;
                                     const u32x2 l0 = *(const u32x2*)(p0 - MA * WFC + 2), l1 = *(const u32x2*)(p1 - MA * WFC + 2);
                                     b0 = u32x4{q0[0], q0[1], q1[0], q1[1]};
                                     b1 = u32x4{q0[2], q0[3], q1[2], q1[3]};
                                     b2 = u32x4{l0[0], l0[1], l1[0], l1[1]};
                                 } else {
-                                    pwb_split8(*(const f32x4*)(S + pwb_off(rb_run[i] + c, 4 * qq + 2 * h)),
-                                               *(const f32x4*)(S + pwb_off(rb_run[i] + c, 4 * qq + 2 * h + 1)), b0, b1, b2);
+                                    pwb_split8(*(const f32x4*)(S + swz_off(rb_run[i] + c, 4 * qq + 2 * h)),
+                                               *(const f32x4*)(S + swz_off(rb_run[i] + c, 4 * qq + 2 * h + 1)), b0, b1, b2);
                                 }
                                 CTX_MF6(acc[i], a0, a1, a2, b0, b1, b2);
                             }
                         }
                         if (more && !(PWB_ABL & 4)) {
-                            if (qq == 0) pwb_wait_vmcnt((NB - 2) * LPW);      // tile t+1 has landed
+                            if (qq == 0) wait_vmcnt_exact<60>((NB - 2) * LPW);      // tile t+1 has landed
 #pragma unroll
                             for (int q = 2 * qq; q < 2 * qq + 2; ++q) {
                                 tpart(q, t + 1, nslot);
@@ -504,18 +475,18 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                 } else {
 #pragma unroll
                 for (int q = 0; q < WFC / 8; ++q) {
-                    const f32x4 av = *(const f32x4*)(S + pwb_off(ra, 2 * q + h));
+                    const f32x4 av = *(const f32x4*)(S + swz_off(ra, 2 * q + h));
 #pragma unroll
                     for (int i = 0; i < PMAXT; ++i) {
                         if (rb_run[i] >= 0 && !(PWB_ABL & 16)) {
-                            const f32x4 bv = *(const f32x4*)(S + pwb_off(rb_run[i] + c, 2 * q + h));
+                            const f32x4 bv = *(const f32x4*)(S + swz_off(rb_run[i] + c, 2 * q + h));
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
                                 acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[i], 0, 0, 0);
                         }
                     }
                     if (more && !(PWB_ABL & 4)) {
-                        if (q == 0) pwb_wait_vmcnt((NB - 2) * LPW);      // tile t+1 has landed
+                        if (q == 0) wait_vmcnt_exact<60>((NB - 2) * LPW);      // tile t+1 has landed
                         tpart(q, t + 1, nslot);
                         tpart(q + 4, t + 1, nslot);
                         if (PDW + PSW > 8) tpart(q + 8, t + 1, nslot);
@@ -570,7 +541,7 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
         // 4 frames of logical piece 4 (G & 1) + (i & 3) of row 8 (G >> 1) + 4 t + (i >> 2) (t = 0, 1) and receives frame
         // 16 (G & 1) + i = c of the rows 8 h + 4 t .. + 3: float offsets inside the slot, K-step 0
         const int trr = 8 * (lane >> 5) + ((lane & 15) >> 2), trp = 4 * ((lane >> 4) & 1) + (lane & 3);
-        const int trb0 = pwb_off(trr, trp), trb1 = pwb_off(trr + 4, trp);
+        const int trb0 = swz_off(trr, trp), trb1 = swz_off(trr + 4, trp);
         if constexpr (KSPLIT) {
             constexpr int AH = AK / 2;                 // k-pairs per wave
             const int rt = j & 1, kh = j >> 1;         // row tile, K half (uniform)
@@ -587,8 +558,8 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                     }
                 }
             }
-            useg = pwb_uniform(useg); uct = pwb_uniform(uct); ucb = pwb_uniform(ucb);
-            const int uflags = pwb_uniform(A.dg[useg].flags);
+            useg = wave_uniform(useg); uct = wave_uniform(uct); ucb = wave_uniform(ucb);
+            const int uflags = wave_uniform(A.dg[useg].flags);
             const trunet_seg& usg = a.seg[useg];
             // some channel of this row tile has a BatchNorm weight of exactly zero (statistics: slow path below)
             const bool uzero = (uflags & TRUNET_DG_STATS) && __builtin_amdgcn_ballot_w64(CZ[ucb + 32 * uct + c][0] == 0.f) != 0;
@@ -636,10 +607,10 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
 #pragma unroll
                 for (int s = 0; s < TRUNET_MAX_SEG; ++s)
                     if (s < useg && pwb_seg_pos(a.seg[s], p).valid) lrow += (a.seg[s].nchan + 31) & ~31;
-                const size_t dstride = pwb_uniform((size_t)usg.L * a.NP);
+                const size_t dstride = wave_uniform((size_t)usg.L * a.NP);
                 const size_t o0 = ((size_t)(32 * uct + rowsel) * usg.L + (sp.valid ? sp.q : 0)) * a.NP;
-                const __amdgpu_buffer_rsrc_t rz = pwb_rsrc(pwb_uniform(A.dg[useg].zmask ? A.dg[useg].zmask + o0 : A.dg[useg].out + o0));
-                const __amdgpu_buffer_rsrc_t ro = pwb_rsrc(pwb_uniform(A.dg[useg].out + o0));
+                const __amdgpu_buffer_rsrc_t rz = buffer_rsrc(wave_uniform(A.dg[useg].zmask ? A.dg[useg].zmask + o0 : A.dg[useg].out + o0));
+                const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(wave_uniform(A.dg[useg].out + o0));
                 const int rowb = (int)(dstride * sizeof(float));
                 const int voff = (int)((4 * h * dstride + c) * sizeof(float));
                 asm volatile("" ::: "memory");
@@ -648,7 +619,7 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                 int slot = 0;
                 for (int t = t0; t < t1; ++t) {
                     const float* S = R_lds + (size_t)slot * SLOT;
-                    const int n0 = pwb_uniform((t - pi * nfc) * WFC);
+                    const int n0 = wave_uniform((t - pi * nfc) * WFC);
                     const int nb = n0 * (int)sizeof(float);
                     float* xs = XB + (size_t)(((t & 1) * 2 + rt) * 2) * 512;       // [sender half][8][64]
                     float zv[8], ov[8];
@@ -678,8 +649,8 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                                 for (int ks = 0; ks < ((PWB_ABL & 32) ? 1 : AH / 8); ++ks) {
                                     const float* q0 = S + trb0 + (2 * kh * AH + 16 * ks) * WFC;
                                     const float* q1 = S + trb1 + (2 * kh * AH + 16 * ks) * WFC;
-                                    const u32x2 h0 = pwb_tr16(q0), h1 = pwb_tr16(q1), m0 = pwb_tr16(q0 + 2), m1 = pwb_tr16(q1 + 2);
-                                    const u32x2 l0 = pwb_tr16(q0 + MA * WFC), l1 = pwb_tr16(q1 + MA * WFC);
+                                    const u32x2 h0 = lds_tr16(q0), h1 = lds_tr16(q1), m0 = lds_tr16(q0 + 2), m1 = lds_tr16(q1 + 2);
+                                    const u32x2 l0 = lds_tr16(q0 + MA * WFC), l1 = lds_tr16(q1 + MA * WFC);
                                     const u32x4 b0 = {h0[0], h0[1], h1[0], h1[1]}, b1 = {m0[0], m0[1], m1[0], m1[1]},
                                                 b2 = {l0[0], l0[1], l1[0], l1[1]};
                                     CTX_MF6(dacc, ap[ks][0], ap[ks][1], ap[ks][2], b0, b1, b2);
@@ -778,7 +749,7 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                 }
             }
             if (u.seg >= 0) u.flags = A.dg[u.seg].flags;
-            u.seg = pwb_uniform(u.seg); u.ct = pwb_uniform(u.ct); u.cb = pwb_uniform(u.cb); u.flags = pwb_uniform(u.flags);
+            u.seg = wave_uniform(u.seg); u.ct = wave_uniform(u.ct); u.cb = wave_uniform(u.cb); u.flags = wave_uniform(u.flags);
             u.zero = (u.flags & TRUNET_DG_STATS) && __builtin_amdgcn_ballot_w64(CZ[u.cb + 32 * u.ct + c][0] == 0.f) != 0;
             return u;
         };
@@ -824,10 +795,10 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                 for (int s = 0; s < TRUNET_MAX_SEG; ++s)
                     if (s < u.seg && pwb_seg_pos(a.seg[s], p).valid) lr += (a.seg[s].nchan + 31) & ~31;
                 r.lrow = lr;
-                r.dstride = pwb_uniform((size_t)sg.L * a.NP);
+                r.dstride = wave_uniform((size_t)sg.L * a.NP);
                 const size_t o = ((size_t)(32 * u.ct) * sg.L + (sp.valid ? sp.q : 0)) * a.NP;
-                r.zb = pwb_uniform(A.dg[u.seg].zmask + o);
-                r.ob = pwb_uniform(A.dg[u.seg].out + o);
+                r.zb = wave_uniform(A.dg[u.seg].zmask + o);
+                r.ob = wave_uniform(A.dg[u.seg].out + o);
                 r.voff = (int)((4 * h * r.dstride + c) * sizeof(float));
             }
             return r;
@@ -839,8 +810,8 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
         // dz rows
         auto dgrad_head = [&](const DUnit& u, const DRun& dr, const Frag& fr, const float* S, int n0)
                               __attribute__((always_inline)) {
-            const __amdgpu_buffer_rsrc_t ro = pwb_rsrc(pwb_uniform(dr.ob));
-            const int rowb = (int)(pwb_uniform(dr.dstride) * sizeof(float));      // bytes between channels
+            const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(wave_uniform(dr.ob));
+            const int rowb = (int)(wave_uniform(dr.dstride) * sizeof(float));      // bytes between channels
             const int nb = n0 * (int)sizeof(float);
 #pragma unroll
             for (int r = 0; r < 16; ++r) { zv[r] = 0.f; ov[r] = 0.f; }
@@ -865,8 +836,8 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
                     for (int ks = 0; ks < ((PWB_ABL & 32) ? 1 : AK / 8); ++ks) {
                         const float* q0 = S + trb0 + 16 * ks * WFC;
                         const float* q1 = S + trb1 + 16 * ks * WFC;
-                        const u32x2 h0 = pwb_tr16(q0), h1 = pwb_tr16(q1), m0 = pwb_tr16(q0 + 2), m1 = pwb_tr16(q1 + 2);
-                        const u32x2 l0 = pwb_tr16(q0 + MA * WFC), l1 = pwb_tr16(q1 + MA * WFC);
+                        const u32x2 h0 = lds_tr16(q0), h1 = lds_tr16(q1), m0 = lds_tr16(q0 + 2), m1 = lds_tr16(q1 + 2);
+                        const u32x2 l0 = lds_tr16(q0 + MA * WFC), l1 = lds_tr16(q1 + MA * WFC);
                         const u32x4 b0 = {h0[0], h0[1], h1[0], h1[1]}, b1 = {m0[0], m0[1], m1[0], m1[1]},
                                     b2 = {l0[0], l0[1], l1[0], l1[1]};
                         CTX_MF6(dacc, fr.ap[ks][0], fr.ap[ks][1], fr.ap[ks][2], b0, b1, b2);
@@ -899,15 +870,15 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
         auto dgrad_tail = [&](auto FLc, const DUnit& u, const DRun& dr, float (&st1)[16], float (&st2)[16], int n0)
                               __attribute__((always_inline)) {
             constexpr int FL = decltype(FLc)::value;
-            const __amdgpu_buffer_rsrc_t ro = pwb_rsrc(pwb_uniform(dr.ob));
-            const int rowb = (int)(pwb_uniform(dr.dstride) * sizeof(float));
+            const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(wave_uniform(dr.ob));
+            const int rowb = (int)(wave_uniform(dr.dstride) * sizeof(float));
             const int nb = n0 * (int)sizeof(float);
             const f32x2* CZs = CZ + u.cb + 32 * u.ct + 4 * h;
             const bool fin = n0 + c < a.N;
             // ZG: z of the statistics read from global memory at its point of use (slow; only when a BatchNorm weight is 0)
             auto rows16 = [&](auto ZGc) __attribute__((always_inline)) {
                 constexpr bool ZG = decltype(ZGc)::value;
-                const __amdgpu_buffer_rsrc_t rz = pwb_rsrc(pwb_uniform(dr.zb));
+                const __amdgpu_buffer_rsrc_t rz = buffer_rsrc(wave_uniform(dr.zb));
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int ml = (r & 3) + 8 * (r >> 2);
@@ -971,7 +942,7 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_kernel(const trunet_pwbwd_args 
             int slot = 0;
             for (int t = t0; t < t1; ++t) {
                 const float* S = R_lds + (size_t)slot * SLOT;
-                const int n0 = pwb_uniform((t - pi * nfc) * WFC);
+                const int n0 = wave_uniform((t - pi * nfc) * WFC);
                 int pending = 0;          // which unit's epilogue waits for the barrier (0 none, 1, 2)
                 if (active(u1, r1, t)) { dgrad_head(u1, r1, af1, S, n0); pending = 1; }
                 if constexpr (SEC) {
