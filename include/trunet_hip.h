@@ -362,6 +362,36 @@ int trunet_stream_features(float* ring, const float* chunk, float* pcen_M, float
  * covering it, dataset.py:293-296: torch.istft's window envelope for the rectangular window); ola shifted by one hop. */
 int trunet_stream_mask_istft(const float* net_out, float* ola, float* out, const float* tw512, int S, float beta, float env,
                              void* stream);
+/* ---- stream pool (streaming.StreamPool): the same two stages for sessions that start, pause and end on their own.  State
+ * tensors hold one row per SLOT at fixed addresses -- ring (slots, 512), pcen_M (slots, 257), ola (slots, 512) -- and a call
+ * handles the n_rows rows of one pass: row i works on slot rows[i][0].  rows: DEVICE array (n_rows, TRUNET_ROW_INTS) int32
+ *   [0] slot   [1] TRUNET_ROW_* flags   [2] t: frame index   [3] a: whole hops received, this row's shift included
+ *   [4] tail: the 0..127 samples after the last whole hop (closing sessions)   [5] env: frames covering the emitted hop
+ *   [6] row of `chunks` (the new hop with TRUNET_ROW_SHIFT, else the tail samples when tail > 0)   [7] row of `out`, -1: none
+ * A frame can be computed while a - 2 <= t <= a, and t <= 1 only while a <= 4 (what lies further back has left the ring).
+ * Frame t is x[reflect(128 t + i - 256, L = 128 a + tail)], i < 512, built from the ring (x[128 a - 512, 128 a)) and the tail.
+ * One real frame per workgroup: a row's results do not depend, bit for bit, on any other row of the call.  Distinct rows of
+ * one call must name distinct slots.  A row whose slot is outside [0, slots), or whose chunk / feature / out row is outside
+ * the given extents, is skipped without touching memory.
+ * trunet_stream_features_rows: SHIFT: ring <- [ring[128:], chunks[row 6]]; unless NOFRAME: frame t -> feat[i] (C, 257) for the
+ * rows i < n_frames (rows from n_frames on must be NOFRAME); C = 4: PCEN with pcen_M[slot] (FIRST: M = s x).  chunks
+ * (n_chunks, 128).  A FIRST row (t = 0) transforms frames 0 and 1 of its session together, paired as the offline entry
+ * points pair them, leaves frame 1's features in stash[slot] (stash: (slots, C, 257)) and the smoother after frame 1 in
+ * pcen_M; the session's next row must be its frame 1 with TRUNET_ROW_STASHED, which copies them to feat[i].
+ * trunet_stream_mask_istft_rows: net_out (n_rows, 8, 257) -> ola[slot] (FIRST: starts from zero) -> out[row 7] (128) = the
+ * final hop / env; FINISH: out rows [7] + 1 and + 2 take the last whole hop (/ 3) and the hop of the tail samples (/ 2).
+ * out (n_out, 128). */
+#define TRUNET_ROW_INTS 8
+#define TRUNET_ROW_SHIFT 1
+#define TRUNET_ROW_FIRST 2
+#define TRUNET_ROW_NOFRAME 4
+#define TRUNET_ROW_FINISH 8
+#define TRUNET_ROW_STASHED 16
+int trunet_stream_features_rows(float* ring, const float* chunks, float* pcen_M, float* stash, float* feat,
+                                const int32_t* rows, int n_rows, int n_frames, int n_chunks, int slots, const float* tw512, int C, float eps, float s,
+                                float alpha, float delta, float r, void* stream);
+int trunet_stream_mask_istft_rows(const float* net_out, float* ola, float* out, const int32_t* rows, int n_rows, int n_out,
+                                  int slots, const float* tw512, float beta, void* stream);
 
 /* ---- offline enhancement of B utterances of any lengths (enhance.py), packed back to back ----
  * audio holds sum L_b samples (L_b >= 257); sample_off[B+1] (prefix of L_b), frame_off[B+1] (prefix of T_b = 1 + L_b/128)

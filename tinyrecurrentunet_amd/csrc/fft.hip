@@ -88,6 +88,17 @@ constexpr int HOPF = 128;    // dataset.py:134
 constexpr int BINS = 257;
 
 // ---------------------------------------------------------------- STFT features
+// one bin of dataset.py:246-272 (amp_to_db :207-211, norm :229-235, sin / cos of the phase) -> magnitude
+__device__ __forceinline__ float spectral_features(float re, float im, float& nm, float& sn, float& cs) {
+    const float mag = sqrtf(re * re + im * im);
+    const float db = 20.f * log10f(fmaxf(mag, 1e-7f)) - 25.f;
+    nm = ((db + 100.f) / 100.f) * 2.f - 1.f;
+    nm = fminf(fmaxf(nm, -1.f), 1.f);
+    sn = 0.f; cs = 1.f;             // angle(0) = 0
+    if (mag > 0.f) { sn = im / mag; cs = re / mag; }
+    return mag;
+}
+
 // grid (ceil(T/2), B); feat: (B*T, C, 257); mag (optional): (B, T, 257)
 __global__ __launch_bounds__(256) void stft_features_kernel(const float* __restrict__ audio, float* __restrict__ feat,
                                                             float* __restrict__ mag_out, const cpx* __restrict__ tw,
@@ -109,14 +120,8 @@ __global__ __launch_bounds__(256) void stft_features_kernel(const float* __restr
         for (int f = 0; f < 2; ++f) {
             const int t = t0 + f;
             if (t >= T) continue;
-            const float re = X[f].x, im = X[f].y;
-            const float mag = sqrtf(re * re + im * im);
-            // dataset.py:207-211 amp_to_db, :229-235 norm
-            const float db = 20.f * log10f(fmaxf(mag, 1e-7f)) - 25.f;
-            float nm = ((db + 100.f) / 100.f) * 2.f - 1.f;
-            nm = fminf(fmaxf(nm, -1.f), 1.f);
-            float sn = 0.f, cs = 1.f;       // angle(0) = 0
-            if (mag > 0.f) { sn = im / mag; cs = re / mag; }
+            float nm, sn, cs;
+            const float mag = spectral_features(X[f].x, X[f].y, nm, sn, cs);
             float* o = feat + ((size_t)(b * T + t) * C) * BINS + k;
             o[0] = nm;
             o[(size_t)(C - 2) * BINS] = sn;
@@ -372,13 +377,8 @@ __global__ __launch_bounds__(256) void stream_features_kernel(float* __restrict_
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             if (f == 1 && !two) continue;
-            const float re = X[f].x, im = X[f].y;
-            const float mag = sqrtf(re * re + im * im);
-            const float db = 20.f * log10f(fmaxf(mag, 1e-7f)) - 25.f;
-            float nm = ((db + 100.f) / 100.f) * 2.f - 1.f;
-            nm = fminf(fmaxf(nm, -1.f), 1.f);
-            float sn = 0.f, cs = 1.f;
-            if (mag > 0.f) { sn = im / mag; cs = re / mag; }
+            float nm, sn, cs;
+            const float mag = spectral_features(X[f].x, X[f].y, nm, sn, cs);
             float* o = feat + ((size_t)(s0 + f) * C) * BINS + k;
             o[0] = nm;
             o[(size_t)(C - 2) * BINS] = sn;
@@ -435,6 +435,151 @@ __global__ __launch_bounds__(256) void stream_mask_istft_kernel(const float* __r
             out[(size_t)s0 * HOPF + i] = acc[i].x / env;
             if (two) out[(size_t)(s0 + 1) * HOPF + i] = acc[i].y / env;
         }
+    }
+}
+
+// ---------------------------------------------------------------- stream pool: independent sessions behind a row table
+// The lockstep kernels above give every stream the same `first` / `env` and pack streams 2i and 2i+1 into one complex FFT, so a
+// stream's last bits depend on its neighbour.  The pool (streaming.StreamPool) runs sessions that start, pause and end on their
+// own: a launch handles the ROWS of one pass, row i works on state slot rows[i].slot, and what was a host scalar is per-row
+// data.  One real frame per workgroup (imaginary half zero: X[k] = Z[k]; the inverse transforms the Hermitian extension and
+// keeps the real part), so nothing a row computes depends on any other row of the launch, bit for bit.  The one pairing is
+// inside a session: frames 0 and 1, which a session owes at the same moment, share one transform exactly as the offline
+// kernels pair them (TRUNET_ROW_FIRST; frame 1 waits in `stash` (slots, C, 257) for the next pass, TRUNET_ROW_STASHED).
+// Frame 0 is symmetric about sample 256, its spectrum real up to (-1)^k with zero crossings between bins: the features of a
+// bin next to a crossing are decided by the rounding of the transform, so this frame is computed the way enhance computes it.
+// Row record = TRUNET_ROW_INTS int32 (trunet_hip.h):
+//   [0] slot  [1] flags  [2] t  [3] a  [4] tail  [5] env  [6] chunk row  [7] out row (-1: none)
+// with t the frame index and a the whole hops received (after this row's shift), tail the 0..127 samples after the last whole
+// hop of a closing session.  Frame t of the centred STFT is x[reflect(128 t + i - 256, L)], L = 128 a + tail; the ring holds
+// x[128 a - 512, 128 a) and the chunk row holds the tail, so every frame of a session's life -- the reflect-built frames 0
+// and 1, the steady state (t = a - 2: the ring as it is) and the end frames at any length -- is built here from kept samples.
+// Sample positions are taken from an origin that moves with the session (a -> min(a, 4), t by the same amount: a frame is
+// computed while t >= a - 2, so nothing left of the origin is ever needed), which keeps 128 t small however old a session is.
+// A row whose slot, chunk row, feature row or out row lies outside the given extents is skipped by its whole workgroup
+// before it touches memory; sample indices are clamped into the staged 640 samples whatever t, a and tail say.
+constexpr int ROW_INTS = TRUNET_ROW_INTS;
+constexpr int POOL_XS = NF + HOPF;
+
+// grid (rows); feat (n_frames, C, 257): row i < n_frames writes feat[i], rows from n_frames on only store their hop
+__global__ __launch_bounds__(256) void stream_features_rows_kernel(float* __restrict__ ring, const float* __restrict__ chunks,
+                                                                   float* __restrict__ pcen_M, float* __restrict__ stash,
+                                                                   float* __restrict__ feat,
+                                                                   const int* __restrict__ rows, int n_frames, int n_chunks,
+                                                                   int slots, const cpx* __restrict__ tw, int C, float eps,
+                                                                   float s, float alpha, float delta, float r, float dr) {
+    __shared__ cpx sa[NF], sb[NF];
+    __shared__ float xs[POOL_XS];
+    const int row = blockIdx.x;
+    const int* rec = rows + (size_t)row * ROW_INTS;
+    const int slot = rec[0], flags = rec[1], crow = rec[6];
+    const int a = min(max(rec[3], 0), 4), t = min(max(rec[2] - (rec[3] - a), 0), 4);
+    const int tail = min(max(rec[4], 0), HOPF - 1);
+    const bool shift = (flags & TRUNET_ROW_SHIFT) != 0, frame = (flags & TRUNET_ROW_NOFRAME) == 0;
+    // all of this is uniform over the workgroup: a bad row leaves without a load or a store
+    if (slot < 0 || slot >= slots) return;
+    if ((shift || tail > 0) && (crow < 0 || crow >= n_chunks)) return;
+    if (frame && row >= n_frames) return;
+    float* rg = ring + (size_t)slot * NF;
+    for (int i = threadIdx.x; i < POOL_XS; i += 256) {
+        float v = 0.f;
+        if (i < NF) {
+            if (shift) v = (i < NF - HOPF) ? rg[i + HOPF] : chunks[(size_t)crow * HOPF + (i - (NF - HOPF))];
+            else v = rg[i];
+        } else if (!shift && i - NF < tail) {
+            v = chunks[(size_t)crow * HOPF + (i - NF)];
+        }
+        xs[i] = v;
+    }
+    __syncthreads();                      // every old ring sample has been read before the shifted ring is written
+    if (shift) {
+        for (int i = threadIdx.x; i < NF; i += 256) rg[i] = xs[i];
+    }
+    if (!frame) return;
+    float* o = feat + ((size_t)row * C) * BINS;
+    float* sh = stash + ((size_t)slot * C) * BINS;
+    if (flags & TRUNET_ROW_STASHED) {                     // frame 1: computed with frame 0, one pass earlier
+        for (int i = threadIdx.x; i < C * BINS; i += 256) o[i] = sh[i];
+        return;
+    }
+    const bool first = (flags & TRUNET_ROW_FIRST) != 0;   // frame 0, and frame 1 in the imaginary half
+    const int L = a * HOPF + tail, base = a * HOPF - NF;
+    for (int i = threadIdx.x; i < NF; i += 256) {
+        const int j = reflect_idx(t * HOPF + i - NF / 2, L) - base;
+        float v1 = 0.f;
+        if (first) {
+            const int j1 = reflect_idx((t + 1) * HOPF + i - NF / 2, L) - base;
+            v1 = xs[min(max(j1, 0), POOL_XS - 1)];
+        }
+        sa[i] = make_float2(xs[min(max(j, 0), POOL_XS - 1)], v1);
+    }
+    const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    for (int k = threadIdx.x; k < BINS; k += 256) {
+        cpx X = Z[k], X1 = make_float2(0.f, 0.f);
+        if (first) split_pair(Z, k, NF, X, X1);
+        float nm, sn, cs;
+        const float mag = spectral_features(X.x, X.y, nm, sn, cs);
+        o[k] = nm;
+        o[(size_t)(C - 2) * BINS + k] = sn;
+        o[(size_t)(C - 1) * BINS + k] = cs;
+        float M = 0.f;
+        if (C == 4) {
+            float* Mp = pcen_M + (size_t)slot * BINS + k;
+            M = first ? s * mag : (1.f - s) * (*Mp) + s * mag;
+            if (!first) *Mp = M;
+            o[BINS + k] = pcen_value(mag, M, eps, alpha, delta, r, dr);
+        }
+        if (first) {
+            const float mag1 = spectral_features(X1.x, X1.y, nm, sn, cs);
+            sh[k] = nm;
+            sh[(size_t)(C - 2) * BINS + k] = sn;
+            sh[(size_t)(C - 1) * BINS + k] = cs;
+            if (C == 4) {
+                M = (1.f - s) * M + s * mag1;
+                pcen_M[(size_t)slot * BINS + k] = M;
+                sh[BINS + k] = pcen_value(mag1, M, eps, alpha, delta, r, dr);
+            }
+        }
+    }
+}
+
+// grid (rows); net_out (rows, 8, 257) -> mask -> irFFT-512 -> the slot's overlap-add tail (TRUNET_ROW_FIRST: the tail starts
+// from zero, whatever the slot's last session left) -> out[out row] = the hop that is final now / env; tail shifted by a hop.
+// TRUNET_ROW_FINISH (the last frame of a session): the two pieces no later frame will touch follow in out rows + 1 and + 2:
+// the last whole hop (three frames cover it) and the hop that holds the tail samples (two frames).
+__global__ __launch_bounds__(256) void stream_mask_istft_rows_kernel(const float* __restrict__ net_out, float* __restrict__ ola,
+                                                                     float* __restrict__ out, const int* __restrict__ rows,
+                                                                     int n_out, int slots, const cpx* __restrict__ tw,
+                                                                     float beta) {
+    __shared__ cpx sa[NF], sb[NF];
+    const int row = blockIdx.x;
+    const int* rec = rows + (size_t)row * ROW_INTS;
+    const int slot = rec[0], flags = rec[1], env = rec[5], orow = rec[7];
+    const bool finish = (flags & TRUNET_ROW_FINISH) != 0;
+    if (slot < 0 || slot >= slots || env < 1) return;                          // uniform over the workgroup
+    if (orow >= 0 ? orow + (finish ? 3 : 1) > n_out : finish) return;
+    for (int k = threadIdx.x; k < BINS; k += 256) {
+        const MaskVals v = mask_vals(net_out + (size_t)row * 8 * BINS + k, BINS, beta);
+        const float M = v.S * v.A;
+        cpx X = make_float2(M * v.cm, M * v.sm);
+        if (k == 0 || k == NF / 2) X.y = 0.f;            // c2r ignores the imaginary part of DC / Nyquist
+        sa[k] = X;
+        if (k > 0 && k < NF / 2) sa[NF - k] = make_float2(X.x, -X.y);
+    }
+    const cpx* z = fft_lds_t<9, true>(sa, sb, tw);
+    float* acc = (float*)((z == sa) ? sb : sa);           // the other buffer: free after the transform
+    float* ol = ola + (size_t)slot * NF;
+    const bool first = (flags & TRUNET_ROW_FIRST) != 0;
+    for (int i = threadIdx.x; i < NF; i += 256) acc[i] = (first ? 0.f : ol[i]) + z[i].x * (1.f / NF);
+    __syncthreads();
+    const float fenv = (float)env;
+    for (int i = threadIdx.x; i < NF; i += 256) {
+        ol[i] = (i + HOPF < NF) ? acc[i + HOPF] : 0.f;
+        if (i < HOPF && orow >= 0) out[(size_t)orow * HOPF + i] = acc[i] / fenv;
+    }
+    if (finish && threadIdx.x < HOPF) {
+        out[(size_t)(orow + 1) * HOPF + threadIdx.x] = acc[HOPF + threadIdx.x] / 3.f;
+        out[(size_t)(orow + 2) * HOPF + threadIdx.x] = acc[2 * HOPF + threadIdx.x] / 2.f;
     }
 }
 
@@ -929,13 +1074,8 @@ __global__ __launch_bounds__(256) void stft_features_ragged_kernel(const float* 
         for (int f = 0; f < 2; ++f) {
             const int t = t0 + f;
             if (t >= T) continue;
-            const float re = X[f].x, im = X[f].y;
-            const float mag = sqrtf(re * re + im * im);
-            const float db = 20.f * log10f(fmaxf(mag, 1e-7f)) - 25.f;
-            float nm = ((db + 100.f) / 100.f) * 2.f - 1.f;
-            nm = fminf(fmaxf(nm, -1.f), 1.f);
-            float sn = 0.f, cs = 1.f;
-            if (mag > 0.f) { sn = im / mag; cs = re / mag; }
+            float nm, sn, cs;
+            const float mag = spectral_features(X[f].x, X[f].y, nm, sn, cs);
             float* o = feat + ((size_t)(u.f0 + t) * C) * BINS + k;
             o[0] = nm;
             o[(size_t)(C - 2) * BINS] = sn;
@@ -1161,6 +1301,27 @@ extern "C" int trunet_stream_mask_istft(const float* net_out, float* ola, float*
     if (!net_out || !ola || !out || !tw512 || S <= 0 || !(env >= 1.f)) return TRUNET_EINVAL;
     hipLaunchKernelGGL(stream_mask_istft_kernel, dim3((S + 1) / 2), dim3(256), 0, ST, net_out, ola, out, (const cpx*)tw512, S,
                        beta, env);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stream_features_rows(float* ring, const float* chunks, float* pcen_M, float* stash, float* feat,
+                                           const int32_t* rows,
+                                           int n_rows, int n_frames, int n_chunks, int slots, const float* tw512, int C,
+                                           float eps, float s, float alpha, float delta, float r, void* stream) {
+    if (!ring || !stash || !rows || !tw512 || n_rows <= 0 || n_frames < 0 || n_frames > n_rows || n_chunks < 0 || slots <= 0 ||
+        (n_frames > 0 && !feat) || (n_chunks > 0 && !chunks) || (C != 3 && C != 4) || (C == 4 && !pcen_M))
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stream_features_rows_kernel, dim3(n_rows), dim3(256), 0, ST, ring, chunks, pcen_M, stash, feat, rows,
+                       n_frames,
+                       n_chunks, slots, (const cpx*)tw512, C, eps, s, alpha, delta, r, powf(delta, r));
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stream_mask_istft_rows(const float* net_out, float* ola, float* out, const int32_t* rows, int n_rows,
+                                             int n_out, int slots, const float* tw512, float beta, void* stream) {
+    if (!net_out || !ola || !out || !rows || !tw512 || n_rows <= 0 || n_out <= 0 || slots <= 0) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stream_mask_istft_rows_kernel, dim3(n_rows), dim3(256), 0, ST, net_out, ola, out, rows, n_out, slots,
+                       (const cpx*)tw512, beta);
     return trunet_launch_status();
 }
 

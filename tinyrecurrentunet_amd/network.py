@@ -279,6 +279,12 @@ class TRUNet(nn.Module):
             state = AudioStream(self, chunk.shape[0], tgru=self.use_tgru if tgru is None else tgru)
         return state.push(chunk), state
 
+    def stream_pool(self, slots, **kw):
+        """A ``streaming.StreamPool`` of ``slots`` independent streaming sessions on this network (eval mode): sessions open,
+        step, pause and close on their own, at any length from 257 samples; see the class for ``tgru`` / ``beta`` / ``int8``."""
+        from .streaming import StreamPool
+        return StreamPool(self, slots, **kw)
+
     def enhance(self, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
         """Offline enhancement of recordings of any lengths (the role of denoise.py:27-97): see enhance.enhance."""
         from .enhance import enhance
