@@ -532,6 +532,27 @@ int trunet_i8_mfma_probe(const void* a, const void* b, int* c, void* stream);
 int trunet_augment_mix(const float* noise, const float* clean, const float* params, float* noisy, float* noise_out, int B,
                        int L, void* stream);
 
+/* ---- reverberant training pairs (build extension: the reference has gain and biquads only) ----
+ * Per row b of (B, L) signals, with h = rir[b][0 .. K_b), K_b = clamp(rir_len[b], 0, Kmax), h[0] the direct path:
+ *   wet[n]  = sum_{k < K_b, k <= n} h[k] clean[n-k]                  (causal, truncated to L)
+ *   target  = clean when early_taps == 0, else the same sum over k < min(early_taps, K_b)   (dereverberation target)
+ *   g       = sqrt(Ps / (Pv 10^(snr_db[b]/10))), Ps = mean(wet^2), Pv = mean(noise^2); g = 1 when snr_db == NULL or when
+ *             Ps or Pv < 1e-20
+ *   noisy   = wet + g noise;  m = max|noisy| > peak > 0  =>  noisy and target are both multiplied by peak / m
+ * A row with K_b == 0 does not reverberate: wet = target = clean bit for bit (not through the transform).  rir == NULL: no
+ * row reverberates (rir_len, ws and Kmax are then unused; Kmax may be 0).  noise is the ALREADY augmented noise (what
+ * trunet_augment_mix writes to noise_out, or to noisy when it is given no clean signal) or NULL; rir is (B, Kmax) with taps at or beyond K_b padding that is never read as data; rir_len
+ * and snr_db are (B) on the device, so a call needs no device -> host copy.  Uniformly partitioned overlap-save convolution
+ * (1024-tap partitions, 2048-point transforms), no atomics: bit for bit repeatable, and a row's result does not depend on
+ * its batch-mates or on Kmax.  ws: trunet_reverb_workspace_bytes(B, L, Kmax) bytes, 8-byte aligned (0 for arguments out of
+ * range); its content is scratch.  TRUNET_EINVAL: NULL clean / noisy / target, rir without rir_len, B, L <= 0, Kmax <= 0
+ * with rir, early_taps < 0, a workspace that is missing or too small, or noisy / target / ws overlapping each other or an
+ * input.  TRUNET_ENOTSUP: Kmax > 65536. */
+size_t trunet_reverb_workspace_bytes(int B, int L, int Kmax);
+int trunet_reverb_mix(const float* clean, const float* noise, const float* rir, const int* rir_len, const float* snr_db,
+                      int early_taps, float peak, float* noisy, float* target, void* ws, size_t ws_bytes, int B, int L,
+                      int Kmax, void* stream);
+
 /* ======================================================================================================================
  * bf16 storage / bf16 MFMA family (BASELINE.json configs[2]; build extension: the reference has no reduced-precision path,
  * SURVEY 8d).  Activations and their gradients are stored as bf16 in the "octet" layout

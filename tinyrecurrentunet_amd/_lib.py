@@ -211,6 +211,8 @@ def _declare(L):
         "trunet_phm_fwd": [p, p, p, i64, f, p],
         "trunet_phm_bwd": [p, p, p, p, p, i64, f, p],
         "trunet_augment_mix": [p, p, p, p, p, i, i, p],
+        "trunet_reverb_workspace_bytes": [i, i, i],
+        "trunet_reverb_mix": [p, p, p, p, p, i, f, p, p, p, C.c_size_t, i, i, i, p],
         "trunet_stream_fwd_grid": [i],
         "trunet_stream_fwd_scratch_floats": [i],
         "trunet_stream_fwd_check": [C.POINTER(C.c_int32), i, i64, i],
@@ -248,6 +250,7 @@ def _declare(L):
     L.trunet_stream_fwd_scratch_floats.restype = C.c_size_t
     L.trunet_loss_scratch_bytes.restype = C.c_size_t
     L.trunet_stoi_workspace_bytes.restype = C.c_size_t
+    L.trunet_reverb_workspace_bytes.restype = C.c_size_t
     L._declared = sorted(sig)
 
 

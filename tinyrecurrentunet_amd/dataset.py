@@ -6,7 +6,10 @@
   torchaudio; here the workers only read and crop (host I/O), the batch goes to the GPU through pinned memory one step
   ahead on a side stream, and gain + both biquads + the clean/noise mix are ONE HIP launch on the whole batch
   (``trunet_augment_mix``, augment.hip).  ``load_CleanNoisyPairDataset`` yields ``(clean, noisy, fileid)`` like the
-  reference's loader (train.py:121), already resident in HBM (the ``.cuda()`` of train.py:124-125 is then a no-op).
+  reference's loader (train.py:121), already resident in HBM (the ``.cuda()`` of train.py:124-125 is then a no-op);
+* an extension for the dereverberation half of TRU-Net: ``Reverb`` and the ``reverb=`` / ``snr_db=`` keywords of the
+  dataset and the loader convolve every pair with a room impulse response, mix at a drawn SNR and guard the peak, as one
+  more GPU stage of the loader (``trunet_reverb_mix``, reverb.hip).
 """
 import math
 import os
@@ -134,18 +137,146 @@ def _read_wav(path):
     return torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)), sr
 
 
+class Reverb:
+    """Room simulation for the training pairs (an extension: the reference has gain and biquads only).
+    ``draw()`` picks a room impulse response per item on the host (Python's ``random``, like ``DataAugment.draw``);
+    ``__call__`` convolves a whole batch on the GPU (``trunet_reverb_mix``, reverb.hip), mixes the augmented noise in at a
+    requested SNR and guards the pair against clipping:
+
+        wet = h * clean (causal, truncated to L);  noisy = wet + g noise;  target = clean ("dry") or h[:early] * clean ("early")
+
+    with ``h[0]`` the direct path, so the target stays time-aligned with ``noisy``.  RIRs come from the wav files of
+    ``rir_root`` (mono or channel 0, at ``sample_rate`` exactly: there is no resampling) or, without a folder, from
+    ``synthetic()``: exponentially decaying Gaussian noise with the drawn RT60 and direct-to-reverberant ratio."""
+
+    PEAK = 0.99
+
+    def __init__(self, rir_root=None, sample_rate=16000, p_reverb=0.5, rt60=(0.2, 1.0), drr_db=(0.0, 15.0),
+                 max_rir_sec=1.0, target="dry", early_ms=50.0):
+        if target not in ("dry", "early"):
+            raise ValueError("Reverb target must be 'dry' or 'early', got %r" % (target,))
+        self.rir_root, self.sample_rate, self.p_reverb = rir_root, int(sample_rate), float(p_reverb)
+        self.rt60, self.drr_db, self.max_rir_sec = tuple(rt60), tuple(drr_db), float(max_rir_sec)
+        self.target, self.early_ms = target, float(early_ms)
+        self.max_taps = max(int(self.max_rir_sec * self.sample_rate), 1)
+        if self.max_taps > 65536:
+            raise ValueError("RIRs of more than 65536 taps are not supported (max_rir_sec * sample_rate = %d)" % self.max_taps)
+        self.files = None
+        if rir_root is not None:
+            self.files = sorted(f for f in os.listdir(rir_root) if f.lower().endswith(".wav"))
+            if not self.files:
+                raise ValueError("no wav files under %s" % rir_root)
+        self._ws = {}
+
+    def __getstate__(self):                      # DataLoader workers get the parameters, not the GPU workspace
+        d = dict(self.__dict__)
+        d["_ws"] = {}
+        return d
+
+    @property
+    def early_taps(self):
+        """taps of the RIR that make the target: 0 = the dry signal"""
+        return 0 if self.target == "dry" else max(int(round(self.early_ms * 1e-3 * self.sample_rate)), 1)
+
+    def synthetic(self, seed, rt60, drr_db):
+        """float64 numpy RIR of min(rt60, max_rir_sec) * sample_rate taps: h[0] = 1, tail g[n] exp(-6.9078 n / (rt60 sr))
+        (60 dB of decay after rt60) with g from default_rng(seed), scaled so that 10 log10(1 / sum_{n>=1} h[n]^2) = drr_db"""
+        sr = self.sample_rate
+        n = max(int(min(float(rt60), self.max_rir_sec) * sr), 1)
+        h = np.zeros(n, dtype=np.float64)
+        h[0] = 1.0
+        if n > 1:
+            t = np.arange(1, n, dtype=np.float64)
+            tail = np.random.default_rng(seed).standard_normal(n - 1) * np.exp(-6.9078 * t / (float(rt60) * sr))
+            h[1:] = tail * math.sqrt(10.0 ** (-float(drr_db) / 10.0) / float(np.sum(tail * tail)))
+        return h
+
+    def prepare(self, h):
+        """a measured RIR -> 1-D float32 tensor: everything before the strongest tap dropped (the direct path moves to tap
+        0), divided by that tap, truncated to max_rir_sec"""
+        h = np.asarray(h, dtype=np.float64).reshape(-1)
+        if h.size == 0 or not np.any(h):
+            raise ValueError("empty or all-zero RIR")
+        i = int(np.argmax(np.abs(h)))
+        h = h[i:i + self.max_taps] / h[i]
+        return torch.from_numpy(np.ascontiguousarray(h, dtype=np.float32))
+
+    def draw(self):
+        """a 1-D float32 RIR, or an empty tensor (no reverberation) with probability 1 - p_reverb"""
+        if random.random() >= self.p_reverb:
+            return torch.empty(0, dtype=torch.float32)
+        if self.files is not None:
+            path = os.path.join(self.rir_root, random.choice(self.files))
+            h, sr = _read_wav(path)
+            if sr != self.sample_rate:
+                raise ValueError("RIR %s is sampled at %d Hz, the pipeline at %d Hz (no resampling)"
+                                 % (path, sr, self.sample_rate))
+            return self.prepare(h.numpy())
+        seed = random.randrange(2 ** 31)
+        rt60 = random.uniform(*self.rt60)
+        drr = random.uniform(*self.drr_db)
+        return torch.from_numpy(self.synthetic(seed, rt60, drr).astype(np.float32))
+
+    def __call__(self, clean, rirs, lens, noise=None, snr_db=None):
+        """clean, noise: (B, 1, L) on the GPU (noise already augmented, or None); rirs: (B, Kmax) zero-padded, lens: (B,)
+        int32 tap counts (0 = the row does not reverberate); snr_db: (B,) or None (unit gain) -> (noisy, target).
+        Asynchronous on the current stream; the workspace is kept per stream and reused."""
+        _need_gpu(clean)
+        dev = clean.device
+        clean = clean.contiguous().float()
+        B, Ln = clean.shape[0], clean.shape[-1]
+        if clean.numel() != B * Ln:
+            raise ValueError("Reverb expects (B, 1, L) signals, got %s" % (tuple(clean.shape),))
+        noise = None if noise is None else noise.to(dev).contiguous().float()
+        if noise is not None and noise.numel() != clean.numel():
+            raise ValueError("noise must have the shape of clean")
+        Kmax = 0 if rirs is None else int(rirs.shape[-1])
+        rirs_d = lens_d = ws = None
+        ws_bytes = 0
+        if Kmax > 0:
+            rirs_d = rirs.to(dev).contiguous().float()
+            lens_d = lens.to(dev).to(torch.int32).contiguous()
+            if rirs_d.shape[0] != B or lens_d.numel() != B:
+                raise ValueError("one RIR row and one length per signal")
+            ws_bytes = int(L.lib().trunet_reverb_workspace_bytes(B, Ln, Kmax))
+            if ws_bytes == 0:
+                raise L.TrunetHipError("trunet_reverb_mix: %d taps are out of range (at most 65536)" % Kmax)
+            key = (str(dev), L.stream())
+            ws = self._ws.get(key)
+            if ws is None or ws.numel() < ws_bytes:
+                ws = self._ws[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        snr_d = None if snr_db is None else torch.as_tensor(snr_db, dtype=torch.float32).to(dev).contiguous()
+        if snr_d is not None and snr_d.numel() != B:
+            raise ValueError("one SNR per signal")
+        noisy, target = torch.empty_like(clean), torch.empty_like(clean)
+        check(L.lib().trunet_reverb_mix(ptr(clean), ptr(noise), ptr(rirs_d), None if lens_d is None else lens_d.data_ptr(),
+                                        ptr(snr_d), self.early_taps, self.PEAK, ptr(noisy), ptr(target),
+                                        None if ws is None else ws.data_ptr(), ws_bytes, B, Ln, Kmax, L.stream()),
+              "reverb_mix")
+        return noisy, target
+
+
 class CleanNoisyPairDataset(Dataset):
     """dataset.py:301-390.  ``root/clean/fileid_{i}.wav`` and noise files in ``root/keyboard`` (training; each noise file
     must be exactly crop length, D19), or the DNS no-reverb test pairs (testing).  An element is
     ``(clean (1, L), noise (1, L), fileid, aug_params (11,))``: reading and the random crop happen here (host I/O in the
     DataLoader workers), the augmentation of the noise and ``noisy = clean + noise`` (:368, :380) are applied to the
     whole batch on the GPU by the loader of ``load_CleanNoisyPairDataset``.  ``root = "synthetic:<items>"`` generates
-    DNS-shaped pairs instead of reading files (benchmarks, smoke runs; no dataset ships with the reference)."""
+    DNS-shaped pairs instead of reading files (benchmarks, smoke runs; no dataset ships with the reference).
 
-    def __init__(self, root="./", subset="training", crop_length_sec=0, sample_rate=48000):
+    ``reverb`` (a ``Reverb``) and ``snr_db`` (a ``(lo, hi)`` range in dB, uniform per item) are extensions; with either set a
+    training element carries two more entries, ``(..., rir (K,), snr or None)``, drawn AFTER everything the 4-tuple draws, and
+    the loader runs the reverberation stage.  With both ``None`` nothing changes, random-number consumption included."""
+
+    def __init__(self, root="./", subset="training", crop_length_sec=0, sample_rate=48000, *, reverb=None, snr_db=None):
         super().__init__()
         assert subset is None or subset in ["training", "testing"]
         self.root, self.subset = root, subset
+        if reverb is not None and reverb.sample_rate != sample_rate:
+            raise ValueError("Reverb is built for %d Hz, the dataset for %d Hz (no resampling)"
+                             % (reverb.sample_rate, sample_rate))
+        self.reverb = reverb
+        self.snr_db = None if snr_db is None else (float(snr_db[0]), float(snr_db[1]))
         self.aug = DataAugment()
         self.crop_length_sec = crop_length_sec
         self.sample_rate = sample_rate
@@ -204,7 +335,11 @@ class CleanNoisyPairDataset(Dataset):
         if len(noise) != len(clean):
             raise ValueError("noise file must be exactly the crop length (%d samples), got %d (dataset.py:380, D19)"
                              % (len(clean), len(noise)))
-        return clean.unsqueeze(0), noise.unsqueeze(0), fileid, params
+        if self.reverb is None and self.snr_db is None:
+            return clean.unsqueeze(0), noise.unsqueeze(0), fileid, params
+        rir = self.reverb.draw() if self.reverb is not None else torch.empty(0, dtype=torch.float32)
+        snr = random.uniform(*self.snr_db) if self.snr_db is not None else None
+        return clean.unsqueeze(0), noise.unsqueeze(0), fileid, params, rir, snr
 
     def __len__(self):
         return len(self.files)
@@ -214,16 +349,27 @@ def _collate_pairs(items):
     clean = torch.stack([it[0] for it in items])
     other = torch.stack([it[1] for it in items])
     params = torch.stack([it[3] for it in items])
-    return clean, other, [it[2] for it in items], params
+    if len(items[0]) == 4:
+        return clean, other, [it[2] for it in items], params
+    # reverberant items: ragged RIRs zero-padded to the batch maximum, their tap counts, the SNRs (or None)
+    lens = torch.tensor([int(it[4].numel()) for it in items], dtype=torch.int32)
+    rirs = torch.zeros((len(items), int(lens.max())), dtype=torch.float32)
+    for b, it in enumerate(items):
+        rirs[b, :lens[b]] = it[4]
+    snr = None if items[0][5] is None else torch.tensor([float(it[5]) for it in items], dtype=torch.float32)
+    return clean, other, [it[2] for it in items], params, rirs, lens, snr
 
 
 class GpuPairLoader:
     """Iterates a DataLoader of (clean, noise, fileid, params) batches and yields ``(clean, noisy, fileid)`` on the GPU:
     batch k+1 is copied host -> HBM (pinned, non-blocking) and augmented + mixed by trunet_augment_mix on a side stream
-    while the consumer trains on batch k; an event orders the hand-over."""
+    while the consumer trains on batch k; an event orders the hand-over.  Batches of a dataset built with ``reverb`` /
+    ``snr_db`` carry RIRs and SNRs and take one more GPU stage (``_stage_reverb``); the first element yielded is then the
+    target of that stage."""
 
     def __init__(self, loader, mix=True):
         self.loader, self.mix = loader, mix
+        self._plain = None                     # the stage without a room, for a dataset with snr_db only
         self.dataset = loader.dataset
         self.sampler = loader.sampler
 
@@ -235,8 +381,10 @@ class GpuPairLoader:
             return None
         if not torch.cuda.is_available():
             raise L.TrunetHipError("the input pipeline augments on the GPU: no MI355X visible")
-        clean, other, fileid, params = batch
         dev = torch.device("cuda", torch.cuda.current_device())
+        if len(batch) == 7:
+            return self._stage_reverb(batch, side, dev)
+        clean, other, fileid, params = batch
         with torch.cuda.stream(side):
             clean_d = clean.to(dev, non_blocking=True).float().contiguous()
             other_d = other.to(dev, non_blocking=True).float().contiguous()
@@ -250,6 +398,31 @@ class GpuPairLoader:
                 noisy = other_d
             ev = side.record_event()
         return clean_d, noisy, fileid, ev
+
+    def _stage_reverb(self, batch, side, dev):
+        """augment the noise (trunet_augment_mix without a clean signal: its output IS the augmented noise), then
+        reverberate, mix at the drawn SNR and guard the peak (trunet_reverb_mix); the first element handed on is the
+        target of the reverberation stage.  Nothing here waits for the device."""
+        clean, other, fileid, params, rirs, lens, snr = batch
+        if not self.mix:
+            raise L.TrunetHipError("reverb / snr_db apply to training items, which carry a noise signal to mix")
+        rv = self.dataset.reverb or self._plain
+        if rv is None:
+            rv = self._plain = Reverb(p_reverb=0.0, sample_rate=self.dataset.sample_rate)
+        with torch.cuda.stream(side):
+            clean_d = clean.to(dev, non_blocking=True).float().contiguous()
+            other_d = other.to(dev, non_blocking=True).float().contiguous()
+            par_d = params.to(dev, non_blocking=True).float().contiguous()
+            rirs_d = rirs.to(dev, non_blocking=True)
+            lens_d = lens.to(dev, non_blocking=True)
+            snr_d = None if snr is None else snr.to(dev, non_blocking=True)
+            B, _, Ln = other_d.shape
+            aug = torch.empty_like(other_d)
+            check(L.lib().trunet_augment_mix(ptr(other_d), None, ptr(par_d), ptr(aug), None, B, Ln, side.cuda_stream),
+                  "augment_mix")
+            noisy, target = rv(clean_d, rirs_d if rirs_d.shape[1] > 0 else None, lens_d, noise=aug, snr_db=snr_d)
+            ev = side.record_event()
+        return target, noisy, fileid, ev
 
     def __iter__(self):
         it = iter(self.loader)
@@ -265,10 +438,14 @@ class GpuPairLoader:
             yield clean, noisy, fileid
 
 
-def load_CleanNoisyPairDataset(root, subset, crop_length_sec, batch_size, sample_rate, num_gpus=1, num_workers=4):
+def load_CleanNoisyPairDataset(root, subset, crop_length_sec, batch_size, sample_rate, num_gpus=1, num_workers=4, *,
+                               reverb=None, snr_db=None):
     """dataset.py:393-412: same arguments (``**trainset_config`` of config/tiny.json + subset, batch_size, num_gpus);
-    DistributedSampler when num_gpus > 1, else shuffle.  Returns an iterable of (clean (B,1,L), noisy (B,1,L), fileid)."""
-    dataset = CleanNoisyPairDataset(root=root, subset=subset, crop_length_sec=crop_length_sec, sample_rate=sample_rate)
+    DistributedSampler when num_gpus > 1, else shuffle.  Returns an iterable of (clean (B,1,L), noisy (B,1,L), fileid).
+    ``reverb`` / ``snr_db`` (keyword-only extensions, see ``Reverb``): the training pairs are reverberated and mixed at a
+    drawn SNR on the GPU; the first element is then the dereverberation target the ``Reverb`` was built for."""
+    dataset = CleanNoisyPairDataset(root=root, subset=subset, crop_length_sec=crop_length_sec, sample_rate=sample_rate,
+                                    reverb=reverb, snr_db=snr_db)
     kwargs = {"batch_size": batch_size, "num_workers": num_workers, "pin_memory": torch.cuda.is_available(),
               "drop_last": False, "collate_fn": _collate_pairs}
     if num_gpus > 1:
