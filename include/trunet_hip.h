@@ -114,7 +114,8 @@ int trunet_conv_gemm(const trunet_gemm_args* h_args, void* stream);
 #define TRUNET_X3_BWD 2
 int trunet_gemm_x3_enable(int on);
 /* launch geometry trunet_conv_gemm picks for these arguments (reporting): kernel instance
- * conv_gemm_kernel<rs, kc, two, epl, nw> (or conv_smallm_kernel<epl> when M <= 8 and !two), ring of nb LDS slots;
+ * conv_gemm_kernel<rs, kc, two, epl, nw, nbt> (or conv_smallm_kernel<epl> when M <= 8 and !two), ring of nb LDS slots
+ * (nbt = nb where the depth is a compile-time instance: !two, epl = 0, rs >= 2, nb 2 or 3; else 0);
  * nw = 8 (256-frame tiles, two waves per SIMD) needs NP to be a multiple of 256 */
 int trunet_conv_gemm_plan(const trunet_gemm_args* h_args, int* rs, int* kc, int* nb, int* two, int* epl, int* nw);
 

@@ -52,4 +52,36 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base) 
 // a wave-uniform value the compiler cannot prove uniform
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// a wave-uniform pointer, as two readfirstlane'd halves: a descriptor built from it stays in SGPRs (no waterfall loop
+// around the buffer operations that use it)
+template <typename T>
+__device__ __forceinline__ T* wave_uniform_ptr(T* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return (T*)(((unsigned long long)hi << 32) | lo);
+}
+
+// 4 / 8 / 16-byte row pieces (float, f32x2, f32x4) through a buffer resource: per-lane byte offset + uniform byte offset.
+// Keep soff = 0 for the 16-byte stores unless two wait states separate the store from the next write to its data registers.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void buffer_store_row(__amdgpu_buffer_rsrc_t r, int voff, int soff, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
+}
+__device__ __forceinline__ void buffer_store_row(__amdgpu_buffer_rsrc_t r, int voff, int soff, f32x2 v) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, 0);
+}
+__device__ __forceinline__ void buffer_store_row(__amdgpu_buffer_rsrc_t r, int voff, int soff, f32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
+}
+// Keeps a scalar fp32 result scalar: plain -O3 packs adjacent scalar adds into v_pk_add_f32, and beside MFMAs a packed f32
+// operation costs more than the two scalar ones it replaces (same result bits either way).  No instruction is emitted, and the
+// arithmetic itself stays visible to the compiler, which places the wait states an MFMA result needs before a vector
+// instruction may read it -- an add written in inline assembly does not get them.
+__device__ __forceinline__ float keep_scalar(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+
 }  // namespace

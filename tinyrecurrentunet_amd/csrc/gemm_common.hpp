@@ -26,6 +26,9 @@ __device__ __forceinline__ void vset(typename BVec<CT>::type& v, int i, float x)
     if constexpr (CT == 1) v = x; else v[i] = x;
 }
 
+// row (of a 32-row slice) that accumulator register r of a 32x32 MFMA tile holds for the lanes 0..31; lanes 32..63: + 4
+__host__ __device__ constexpr int frag_row(int r) { return (r & 3) + 8 * (r >> 2); }
+
 struct SegPos { bool valid; int q; };
 
 __device__ __forceinline__ SegPos seg_pos(const trunet_seg& sg, int p) {

@@ -15,6 +15,7 @@
 // Epilogue: bias / ReLU-mask / accumulate, vector stores, per-channel statistics kept in registers
 // across all tiles and written once per workgroup (deterministic two-stage reduction).
 #include <cstdlib>
+#include <type_traits>
 #include "common.hpp"
 
 #include "gemm_common.hpp"
@@ -33,8 +34,13 @@ namespace {
 // NW = 4: 128-frame tiles, one wave per SIMD.  NW = 8: 256-frame tiles, the second group of four waves takes the
 // upper 128 frames of every tile -- same per-wave bookkeeping, twice the MFMAs between two barriers, and two waves
 // per SIMD that fill each other's LDS/issue gaps inside the MFMA phase.
-template <int RS, int KC, bool TWO, int EPL, int NW>
-__global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_gemm_kernel(const trunet_gemm_args a, const int NB) {
+// NBT: the ring depth as a compile-time constant (the counted waits become immediates, the slot arithmetic constants), 0 = the
+// run-time argument nb_rt.  buf_rows: the host found 32 output rows + one tile below 2^31 bytes, so rows can be addressed as
+// buffer resource + 32-bit offsets (fast epilogue); otherwise every row keeps its 64-bit address.
+template <int RS, int KC, bool TWO, int EPL, int NW, int NBT>
+__global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_gemm_kernel(const trunet_gemm_args a, const int nb_rt,
+                                                                                          const int buf_rows) {
+    const int NB = NBT ? NBT : nb_rt;
     constexpr int FT = 32 * NW;        // frames per tile
     constexpr int CT = RS;            // column tiles (of 32 frames) per wave
     constexpr int CG = 4 / RS;        // column groups
@@ -188,6 +194,34 @@ __global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_g
         // s_setprio for it (no per-phase flips) is worth +19 % on the 64-row launches (pw 192 -> 64: 66 -> 79 TF) and
         // is neutral at 128 rows.
         if (NW == 8 && wave8 >= 4) __builtin_amdgcn_s_setprio(1);
+        // ---- epilogue state that no tile changes.  Without tensor operands in the epilogue this lane's 16 rows keep their
+        // bias in registers (it was one LDS round trip per row and tile); the instances with zmask / accumulate rows have no
+        // registers to spare for bias, e0, e1, e2 and read them from LDS as before.  The flag tests are wave-uniform and
+        // made once.
+        constexpr bool PREG = EPL == 0;
+        float bvr[PREG ? 16 : 1];
+        if (PREG) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) bvr[r] = E_lds[32 * rs + frag_row(r) + 4 * h];
+        }
+        const bool relu = (a.epi & TRUNET_EPI_RELU) != 0;
+        const bool stats = (a.epi & TRUNET_EPI_STATS) != 0;
+        // Fast epilogue: a full row block (no per-row m < M predicate), no ReLU, rows through a buffer resource whose
+        // base is re-based per tile and group of 8 rows on the scalar unit, four per-lane voffsets for the whole kernel.
+        // The instances with tensor operands in the epilogue (EPL > 0) keep the general path: they sit at the register limit
+        // of their occupancy, and the fast path's per-lane offsets would spill.
+#ifdef TRUNET_EPI_NT
+        const bool fast = false;
+#else
+        const bool fast = EPL == 0 && buf_rows && !relu && mblk * MB + MB <= a.M;
+#endif
+        const size_t rowstride = (size_t)a.out_L * a.NP;
+        // row frag_row(r) + 4 h of the wave's slice = voffq[r & 3] (rows 0..3, + 4 h) past the base of row group r >> 2
+        int voffq[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) voffq[q] = fast ? (int)(((4 * h + q) * rowstride + CT * c) * sizeof(float)) : 0;
+        const size_t row0 = (size_t)(mblk * MB + 32 * rs + a.m_out_off) * a.out_L + a.out_pos_off;
+        const int wcol = 128 * half + (32 * RS) * cg;                               // first frame of the wave inside a tile
         // ---- pipeline prologue
         it_enter_tile<KC, FT>(a, cur);
         ChunkIt ld = cur, ldlast = cur;
@@ -214,7 +248,9 @@ __global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_g
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
             const int tp = cur.p;
-            const int nb = cur.n0 + 128 * half + (32 * RS) * cg + CT * c;
+            const int tn0 = cur.n0;
+            const int nb = tn0 + wcol + CT * c;
+            const size_t tbase = (row0 + tp) * a.NP + tn0 + wcol;       // wave-uniform: this lane's row 0 is at tbase + voffq[0]
             bvec zv[16], ov[16];
             bool last = false;
             while (!last) {                              // ---- chunks of the tile
@@ -223,7 +259,7 @@ __global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_g
                 if (EPL > 0 && last) {                   // epilogue operands: issued before the MFMAs
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int ml = 32 * rs + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int ml = 32 * rs + frag_row(r) + 4 * h;
                         const int m = min(mblk * MB + ml, a.M - 1);
                         const size_t off = ((size_t)(m + a.m_out_off) * a.out_L + tp + a.out_pos_off) * a.NP + nb;
                         zv[r] = *(const bvec*)(a.zmask + off);
@@ -275,45 +311,76 @@ __global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_g
                 slot = (slot + 1 == NB) ? 0 : slot + 1;
                 cur = nxt;
             }
-            // ---- epilogue of the tile
+            // ---- epilogue of the tile.  The fp32 operations on data and their order are those of the general path below:
+            // acc + bias, store; statistics st1 += x, st2 = fma(x, x, st2).
+            if (fast) {
+                // One descriptor per group of 8 rows (registers 4 g .. 4 g + 3), re-based on the scalar unit; the offset field
+                // of the stores stays 0.  (A store of more than 8 bytes WITH an SGPR offset must not be followed within two
+                // wait states by a write to its data registers, and the next row's adds do follow it.)
+                __amdgpu_buffer_rsrc_t ro[4];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ml = 32 * rs + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int m = mblk * MB + ml;
-                const int mg = m + a.m_out_off;
-                const size_t off = ((size_t)mg * a.out_L + tp + a.out_pos_off) * a.NP + nb;
-                bvec val;
-                const float bv = E_lds[ml];
+                for (int g = 0; g < 4; ++g) ro[g] = buffer_rsrc(wave_uniform_ptr(a.out + tbase + 8 * g * rowstride));
+                // with_stats / partial: uniform per tile.  Only the tile that crosses N holds frames the statistics must not see.
+                auto rows = [&](auto with_stats, auto partial) {
 #pragma unroll
-                for (int t = 0; t < CT; ++t) vset<CT>(val, t, acc[t][r] + bv);
-                if (EPL > 1) {
+                    for (int r = 0; r < 16; ++r) {
+                        bvec val;
 #pragma unroll
-                    for (int t = 0; t < CT; ++t) vset<CT>(val, t, vget<CT>(val, t) + vget<CT>(ov[r], t));
-                }
-                float e2 = 0.f;
-                if (EPL > 0) {
-                    const float e0 = E_lds[MB + ml], e1 = E_lds[2 * MB + ml];
-                    e2 = E_lds[3 * MB + ml];
+                        for (int t = 0; t < CT; ++t) vset<CT>(val, t, keep_scalar(acc[t][r] + bvr[PREG ? r : 0]));
+                        buffer_store_row(ro[r >> 2], voffq[r & 3], 0, val);
+                        if (decltype(with_stats)::value) {
 #pragma unroll
-                    for (int t = 0; t < CT; ++t)
-                        vset<CT>(val, t, (fmaf(e0, vget<CT>(zv[r], t), e1) > 0.f) ? vget<CT>(val, t) : 0.f);
-                }
-                if (a.epi & TRUNET_EPI_RELU) {
+                            for (int t = 0; t < CT; ++t) {
+                                const float x = (decltype(partial)::value && nb + t >= a.N) ? 0.f : vget<CT>(val, t);
+                                st1[r] = keep_scalar(st1[r] + x);
+                                st2[r] = keep_scalar(fmaf(x, x, st2[r]));
+                            }
+                        }
+                    }
+                };
+                if (!stats) rows(std::false_type(), std::false_type());
+                else if (tn0 + FT > a.N) rows(std::true_type(), std::true_type());
+                else rows(std::true_type(), std::false_type());
+            } else {
 #pragma unroll
-                    for (int t = 0; t < CT; ++t) vset<CT>(val, t, fmaxf(vget<CT>(val, t), 0.f));
-                }
+                for (int r = 0; r < 16; ++r) {
+                    const int ml = 32 * rs + frag_row(r) + 4 * h;
+                    const int m = mblk * MB + ml;
+                    const int mg = m + a.m_out_off;
+                    const size_t off = ((size_t)mg * a.out_L + tp + a.out_pos_off) * a.NP + nb;
+                    bvec val;
+                    const float bv = PREG ? bvr[PREG ? r : 0] : E_lds[ml];
+#pragma unroll
+                    for (int t = 0; t < CT; ++t) vset<CT>(val, t, acc[t][r] + bv);
+                    if (EPL > 1) {
+#pragma unroll
+                        for (int t = 0; t < CT; ++t) vset<CT>(val, t, vget<CT>(val, t) + vget<CT>(ov[r], t));
+                    }
+                    float e2 = 0.f;
+                    if (EPL > 0) {
+                        const float e0 = E_lds[MB + ml], e1 = E_lds[2 * MB + ml];
+                        e2 = E_lds[3 * MB + ml];
+#pragma unroll
+                        for (int t = 0; t < CT; ++t)
+                            vset<CT>(val, t, (fmaf(e0, vget<CT>(zv[r], t), e1) > 0.f) ? vget<CT>(val, t) : 0.f);
+                    }
+                    if (relu) {
+#pragma unroll
+                        for (int t = 0; t < CT; ++t) vset<CT>(val, t, fmaxf(vget<CT>(val, t), 0.f));
+                    }
 #ifdef TRUNET_EPI_NT
-                if (m < a.M) __builtin_nontemporal_store(val, (bvec*)(a.out + off));
+                    if (m < a.M) __builtin_nontemporal_store(val, (bvec*)(a.out + off));
 #else
-                if (m < a.M) *(bvec*)(a.out + off) = val;
+                    if (m < a.M) *(bvec*)(a.out + off) = val;
 #endif
-                if (a.epi & TRUNET_EPI_STATS) {
+                    if (stats) {
 #pragma unroll
-                    for (int t = 0; t < CT; ++t) {
-                        const float x = (nb + t < a.N && m < a.M) ? vget<CT>(val, t) : 0.f;
-                        st1[r] += x;
-                        if (EPL > 0) st2[r] = fmaf(x, vget<CT>(zv[r], t) - e2, st2[r]);
-                        else st2[r] = fmaf(x, x, st2[r]);
+                        for (int t = 0; t < CT; ++t) {
+                            const float x = (nb + t < a.N && m < a.M) ? vget<CT>(val, t) : 0.f;
+                            st1[r] += x;
+                            if (EPL > 0) st2[r] = fmaf(x, vget<CT>(zv[r], t) - e2, st2[r]);
+                            else st2[r] = fmaf(x, x, st2[r]);
+                        }
                     }
                 }
             }
@@ -498,15 +565,30 @@ int launch_smallm(const trunet_gemm_args* h, hipStream_t st) {
     return trunet_launch_status();
 }
 
-template <int RS, int KC, bool TWO, int EPL, int NW>
-int launch_gemm_nw(const trunet_gemm_args* h, int NB, size_t lds, hipStream_t st) {
+template <int RS, int KC, bool TWO, int EPL, int NW, int NBT>
+int launch_gemm_nb(const trunet_gemm_args* h, int NB, size_t lds, hipStream_t st) {
     const int mb = 32 * RS;
     dim3 grid((NW == 4 && EPL == 0 && lds <= 80 * 1024) ? 2 * TRUNET_NUM_CU : TRUNET_NUM_CU, (h->M + mb - 1) / mb);
-    auto kern = conv_gemm_kernel<RS, KC, TWO, EPL, NW>;
+    auto kern = conv_gemm_kernel<RS, KC, TWO, EPL, NW, NBT>;
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return TRUNET_ELAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, *h, NB);
+    // buffer-addressed rows: the 32 rows of a wave (row stride out_L * NP floats) plus one tile stay below 2^31 bytes from
+    // the wave's per-tile base.  A launch that cannot meet this keeps 64-bit row addresses.
+    const long long span = 32LL * h->out_L * h->NP * (long long)sizeof(float) + 32 * NW * (long long)sizeof(float);
+    const int buf_rows = span < (1LL << 31) ? 1 : 0;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, *h, NB, buf_rows);
     return trunet_launch_status();
+}
+
+// The forward launches (one-tensor prologue, no tensor-operand epilogue, 64 rows and more) get the ring depths the plan
+// produces for them, 2 and 3, as compile-time instances; every other launch passes the depth at run time.
+template <int RS, int KC, bool TWO, int EPL, int NW>
+int launch_gemm_nw(const trunet_gemm_args* h, int NB, size_t lds, hipStream_t st) {
+    if constexpr (!TWO && EPL == 0 && RS >= 2) {
+        if (NB == 2) return launch_gemm_nb<RS, KC, TWO, EPL, NW, 2>(h, NB, lds, st);
+        if (NB == 3) return launch_gemm_nb<RS, KC, TWO, EPL, NW, 3>(h, NB, lds, st);
+    }
+    return launch_gemm_nb<RS, KC, TWO, EPL, NW, 0>(h, NB, lds, st);
 }
 
 template <int RS, int KC, bool TWO, int EPL>

@@ -91,7 +91,9 @@ def _gemm_kernel_name(a):
         return "conv_smallm_kernel<%d>" % epl
     if nw < 0:              # the three-term bf16-split kernel (gemm_x3.hip)
         return "conv_gemm_x3_kernel<%d>" % rs
-    return "conv_gemm_kernel<%d, %d, %s, %d, %d>" % (rs, kc, "true" if two else "false", epl, nw)
+    # last argument: the ring depth as a compile-time constant (launch_gemm_nw in gemm_conv.hip), 0 = run-time depth
+    nbt = nb if (not two and epl == 0 and rs >= 2 and nb in (2, 3)) else 0
+    return "conv_gemm_kernel<%d, %d, %s, %d, %d, %d>" % (rs, kc, "true" if two else "false", epl, nw, nbt)
 
 
 def _seg_positions(s, p0, P):
