@@ -9,12 +9,19 @@ offsets / a second operand segment -- nothing is copied.  Backward mirrors this:
 produces dy (ReLU-masked) plus the BatchNorm-backward sums, one wgrad launch per weight.
 
 PyTorch is used for device memory only; all arithmetic is in libtrunet_hip.so.
+
+The layer schedule (``_pw``, ``_convT``, ``_dw``, ``_pw_bwd``, ``_bwd_tr``, ``_bwd_dsc`` and the decoder / encoder walks of
+``backward``) exists once and is written against a kernel family: ``Fp32Kernels`` here, ``engine_bf16.Bf16Kernels`` for
+bf16 storage.  A family holds what differs between the precisions -- tensor layout, ``Act`` class, dz segment, the GEMM /
+weight-gradient / fused-backward / depthwise launches -- and ``_fam(act)`` picks it by the activation a layer reads.
 """
+import ctypes
+import os
+import types
+
 import torch
 
 from . import _lib as L
-import os
-
 from ._lib import (DG_ACCUM, DG_MASK, DG_PREZERO, DG_STATS, DG_STORE, EPI_ACCUM, EPI_BIAS, EPI_MASK, EPI_PREZERO, EPI_STATS, PRO_BNBWD,
                    PRO_BNRELU, PRO_NONE, ConvtBwdArgs, GemmArgs, PwBwdArgs, WgradArgs, check, make_seg, ptr)
 
@@ -71,6 +78,25 @@ class _Timed:
         return False
 
 
+def _launch(fn, what, rec, *args, may_refuse=False):
+    """One library launch fn(*args), checked under the name `what`; returns its code.  may_refuse: TRUNET_ENOTSUP is not an
+    error (a fused kernel that does not take the shape: the caller runs the separate launches).  With PROFILE set the
+    launch is timed as the _Timed record rec() describes, (kernel name, flops or bytes, tag[, nbytes]); rec is not called
+    otherwise, so the unprofiled step (host-bound) never works out kernel names or position sums."""
+    if PROFILE is None:
+        rc = fn(*args)
+    else:
+        with _Timed(*rec()):
+            rc = fn(*args)
+    if not (may_refuse and rc == L.TRUNET_ENOTSUP):
+        check(rc, what)
+    return rc
+
+
+def _shape_tag(M, segs, P):
+    return "M%d K%s P%d" % (M, "+".join(str(s.nchan) for s in segs), P)
+
+
 def _gemm_rs(M, segs):
     """Mirror of pick_rs() in gemm_conv.hip (which template instance a launch uses)."""
     nck = sum((s.nchan + 31) // 32 for s in segs)
@@ -83,9 +109,8 @@ def _gemm_rs(M, segs):
 def _gemm_kernel_name(a):
     """Exact symbol (template arguments included) of the kernel trunet_conv_gemm launches for `a`, so that
     bench.py's per-kernel numbers can be matched against rocprofv3's kernel names."""
-    import ctypes as C
-    v = [C.c_int() for _ in range(6)]
-    check(L.lib().trunet_conv_gemm_plan(a, *[C.byref(x) for x in v]), "conv_gemm_plan")
+    v = [ctypes.c_int() for _ in range(6)]
+    check(L.lib().trunet_conv_gemm_plan(a, *[ctypes.byref(x) for x in v]), "conv_gemm_plan")
     rs, kc, nb, two, epl, nw = [x.value for x in v]
     if a.M <= 8 and not two:
         return "conv_smallm_kernel<%d>" % epl
@@ -195,6 +220,220 @@ class Workspace:
         return b
 
 
+class Fp32Kernels:
+    """The fp32 kernel family under the layer schedule: activations [C][L][NP], segments of ``make_seg``, the
+    ``trunet_conv_*`` / ``trunet_pw_bwd`` / ``trunet_convt_bwd`` / ``trunet_dwconv_*`` launches.  ``eng`` owns the
+    gradient partial images and ``_bn_bwd``."""
+    Act = Act
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    @staticmethod
+    def alloc(w, name, C, Ln, NP):
+        return w.get(name, (C, Ln, NP))
+
+    @staticmethod
+    def dz_seg(dy_, z_, bn_, C, Ln, **kw):
+        if bn_ is None:
+            return make_seg(dy_, C, Ln, mode=PRO_NONE, **kw)
+        return make_seg(dy_, C, Ln, mode=PRO_BNBWD, src1=z_, c0=bn_.ca, c1=bn_.cb, c2=bn_.cc, **kw)
+
+    @staticmethod
+    def gemm_args(*, N, NP, P, M, out, out_L, W, ldw_m, ldw_c, segs, p_begin=0, out_pos_off=0, m_out_off=0, w_m_off=0,
+                  epi=0, bias=None):
+        a = GemmArgs()
+        a.NP, a.N, a.P, a.p_begin = NP, N, P, p_begin
+        a.M, a.m_out_off, a.out_L, a.out_pos_off = M, m_out_off, out_L, out_pos_off
+        a.ldw_m, a.ldw_c, a.w_m_off = ldw_m, ldw_c, w_m_off
+        a.nseg = len(segs)
+        for i, s in enumerate(segs):
+            a.seg[i] = s
+        a.out, a.W = ptr(out), ptr(W)
+        if bias is not None:
+            epi |= EPI_BIAS
+            a.bias = ptr(bias)
+        a.epi = epi
+        return a
+
+    def gemm(self, w, *, segs, zmask=None, e0=None, e1=None, e2=None, stats=None, **kw):
+        a = self.gemm_args(segs=segs, **kw)
+        if zmask is not None:
+            a.epi |= EPI_MASK
+            a.zmask, a.e0, a.e1, a.e2 = ptr(zmask), ptr(e0), ptr(e1), ptr(e2)
+        nparts = 0
+        if stats is not None:
+            a.epi |= EPI_STATS
+            nparts = L.lib().trunet_conv_gemm_nparts(a.M)
+            part = w.flat("partials", nparts * stats * 2, zero=True)
+            a.partials, a.M_stat = ptr(part), stats
+            if w.take_clean("partials"):
+                a.epi |= EPI_PREZERO
+
+        def rec():
+            fl = 2.0 * a.N * a.M * sum(s.nchan * _seg_positions(s, a.p_begin, a.P) for s in segs)
+            tag = "%s%s%s" % (_shape_tag(a.M, segs, a.P), " two" if any(s.mode == PRO_BNBWD for s in segs) else "",
+                              " mask" if zmask is not None else "")
+            return _gemm_kernel_name(a), fl, tag
+        _launch(L.lib().trunet_conv_gemm, "conv_gemm", rec, a, L.stream())
+        return nparts
+
+    def wgrad(self, w, *, N, NP, P, M, dz, dz_L, dz_bn, W, ldw_m, ldw_c, segs, grads, bias=None, a_pos_off=0,
+              a_m_off=0, w_m_off=0, b_off=0, dz1=None):
+        eng = self.eng
+        a = WgradArgs()
+        a.NP, a.N, a.P, a.p_begin = NP, N, P, 0
+        a.M, a.a_L, a.a_pos_off, a.a_m_off = M, dz_L, a_pos_off, a_m_off
+        a.ldw_m, a.ldw_c, a.w_m_off = ldw_m, ldw_c, w_m_off
+        a.nseg = len(segs)
+        for i, s in enumerate(segs):
+            a.seg[i] = s
+        a.a0 = ptr(dz)
+        if dz_bn is not None:
+            if dz1 is None:
+                raise L.TrunetHipError("weight gradient behind a BatchNorm needs the raw conv output next to dy")
+            a.a_mode = PRO_BNBWD
+            a.a1, a.ac0, a.ac1, a.ac2 = ptr(dz1), ptr(dz_bn.ca), ptr(dz_bn.cb), ptr(dz_bn.cc)
+        else:
+            a.a_mode = PRO_NONE
+        a.w_numel = eng._wg_total                       # image stride of the shared buffer
+        a.w_partials = eng._wg_slot(W)
+        if bias is not None:
+            a.b_partials = eng._wg_slot(bias)
+            a.b_stride, a.b_off = eng._wg_total, b_off
+        _launch(L.lib().trunet_conv_wgrad, "conv_wgrad",
+                lambda: ("conv_wgrad_kernel<%s>" % ("true" if dz_bn is not None else "false"),
+                         2.0 * N * M * sum(s.nchan * _seg_positions(s, 0, P) for s in segs), _shape_tag(M, segs, P)),
+                a, L.stream())
+
+    @staticmethod
+    def fuse_pw(M=None):
+        """The fusion switch of a pointwise backward.  M: the rows of a decoder layer -- decoder.5's 8-row layer runs on
+        trunet_pw_bwd with its dz block padded to one 32-row MFMA tile unless TRUNET_FUSED_THIN=0 keeps its three
+        separate launches (conv_wgrad + two conv_gemm)."""
+        return FUSED_PWBWD and (M is None or M % 32 == 0 or (M <= 32 and FUSED_THIN))
+
+    def pw_bwd(self, w, N, NP, P, M, dz, dz1, dz_bn, W, bias, segs, outs, grads, K, a_m_off=0, w_m_off=0, b_off=0,
+               must_fuse=False):
+        """trunet_pw_bwd; False when the kernel does not take the shape (TRUNET_ENOTSUP: e.g. tensors beyond its 32-bit row
+        offsets, thin layers) and the caller runs the separate launches.
+        a_m_off / w_m_off / b_off: a ROW BLOCK of a wider layer (the GRU input projection, 2 x 192 rows, as blocks of
+        128 + 64): first dz row, first weight row inside W, first bias row."""
+        lib, eng = L.lib(), self.eng
+        a = PwBwdArgs()
+        aw = a.w
+        aw.NP, aw.N, aw.P, aw.p_begin = NP, N, P, 0
+        aw.M, aw.a_L, aw.a_pos_off, aw.a_m_off = M, P, 0, a_m_off
+        aw.ldw_m, aw.ldw_c, aw.w_m_off = K, 1, w_m_off
+        aw.nseg = len(segs)
+        aw.a0, aw.a1 = ptr(dz), ptr(dz1)
+        aw.a_mode = PRO_BNBWD
+        aw.ac0, aw.ac1, aw.ac2 = ptr(dz_bn.ca), ptr(dz_bn.cb), ptr(dz_bn.cc)
+        aw.w_numel = eng._wg_total                      # image stride of the shared buffer
+        aw.w_partials, aw.b_partials = eng._wg_slot(W), eng._wg_slot(bias)
+        aw.b_stride, aw.b_off = eng._wg_total, b_off
+        a.W = ptr(W.data)
+        nparts = lib.trunet_pw_bwd_nparts()
+        stat_parts = []
+        for i, (sg, o) in enumerate(zip(segs, outs)):
+            aw.seg[i] = sg
+            d = a.dg[i]
+            d.out = ptr(o["out"])
+            fl = DG_STORE
+            src = o.get("src")
+            if src is not None:
+                fl |= DG_MASK
+                d.zmask = ptr(src.t)
+                if src.bn is not None:
+                    fl |= DG_STATS
+                    part = w.flat("pwb_partials%d" % i, nparts * sg.nchan * 2, zero=True)
+                    d.e2, d.partials = ptr(src.bn.mean), ptr(part)
+                    stat_parts.append((src.bn, "pwb_partials%d" % i))
+                    if w.take_clean("pwb_partials%d" % i):
+                        fl |= DG_PREZERO
+            if o.get("accum"):
+                fl |= DG_ACCUM
+            d.flags = fl
+
+        def rec():
+            fl_ = 4.0 * N * M * sum(s.nchan * _seg_positions(s, 0, P) for s in segs)
+            # the instance trunet_pw_bwd launches, as rocprofv3 prints it: <AK, SEC, KSPLIT> (KSPLIT: two source row tiles)
+            ksplit = K == 64 and os.environ.get("TRUNET_PWB_KSPLIT", "1") != "0"
+            name = "pw_bwd_kernel<%d, %s, %s, %s>" % (16 if M <= 32 else (32 if M <= 64 else 64), "true" if K == 192 else "false",
+                                                      "true" if ksplit else "false",
+                                                      "true" if lib.trunet_gemm_x3_enable(-1) & L.X3_BWD else "false")
+            # algorithmic bytes: dy and z_y once, every source row once, every gradient row written once (read as well
+            # where it accumulates), fp32, valid frames only
+            by_ = 4.0 * N * (2 * M * P + sum((3 if o.get("accum") else 2) * s.nchan * _seg_positions(s, 0, P)
+                                             for s, o in zip(segs, outs)))
+            return name, fl_, _shape_tag(M, segs, P), by_
+        rc = _launch(lib.trunet_pw_bwd, "pw_bwd", rec, a, L.stream(), may_refuse=True)
+        if rc == 0:
+            for bn, pname in stat_parts:
+                eng._bn_bwd(w, bn, nparts, grads, part_name=pname)
+            return True
+        for _, pname in stat_parts:          # nothing was launched: the statistics buffers are as clean as before
+            w.pending.discard(pname)
+        if must_fuse:
+            check(rc, "pw_bwd")
+        return False
+
+    def convt_bwd(self, w, N, NP, ct, a_pw, Lo, dy, z, bn, dy_pw, grads):
+        """Fused backward of ConvTranspose1d(64 -> 64) + BatchNorm (trunet_convt_bwd): weight / bias gradient, the data
+        gradient at the pointwise BatchNorm's output (masked) and its BatchNorm-backward sums in one pass over (dy, z,
+        source).  False when switched off (TRUNET_FUSED_CONVT=0) or when the kernel does not support the layer
+        (TRUNET_ENOTSUP): the caller takes the separate launches."""
+        if not FUSED_CONVT:
+            return False
+        lib, eng = L.lib(), self.eng
+        k, s_, pad = ct.kernel_size[0], ct.stride[0], ct.padding[0]
+        a = ConvtBwdArgs()
+        a.NP, a.N, a.Lin, a.Lout, a.K, a.S, a.pad = NP, N, a_pw.L, Lo, k, s_, pad
+        a.Ci, a.Co = ct.in_channels, ct.out_channels
+        if a.Ci != 64 or a.Co != 64:
+            return False
+        nparts = lib.trunet_convt_bwd_nparts()
+        part = w.flat("ct_partials", nparts * a.Ci * 2)
+        a.dy, a.z = ptr(dy), ptr(z)
+        a.ca, a.cb, a.cc = ptr(bn.ca), ptr(bn.cb), ptr(bn.cc)
+        a.src, a.s_scale, a.s_shift, a.s_mean = ptr(a_pw.t), ptr(a_pw.bn.scale), ptr(a_pw.bn.shift), ptr(a_pw.bn.mean)
+        a.W, a.dsrc, a.partials = ptr(ct.weight.data), ptr(dy_pw), ptr(part)
+        a.w_numel = eng._wg_total
+        a.w_partials, a.b_partials = eng._wg_slot(ct.weight), eng._wg_slot(ct.bias)
+        a.b_stride, a.b_off = eng._wg_total, 0
+
+        def rec():
+            fl = 4.0 * N * a.Ci * a.Co * sum(1 for q in range(a_pw.L) for kk in range(k) if 0 <= q * s_ - pad + kk < Lo)
+            x3 = lib.trunet_gemm_x3_enable(-1) & L.X3_BWD
+            return "convt_bwd_kernel<%d, %d, %s>" % (k, s_, "true" if x3 else "false"), fl, "L%d" % a_pw.L
+        if _launch(lib.trunet_convt_bwd, "convt_bwd", rec, a, L.stream(), may_refuse=True) == L.TRUNET_ENOTSUP:
+            return False
+        eng._bn_bwd(w, a_pw.bn, nparts, grads, part_name="ct_partials")
+        return True
+
+    @staticmethod
+    def dw_nparts(NP, Ln, bwd):
+        return L.lib().trunet_dwconv_bwd_nparts(Ln) if bwd else L.lib().trunet_dwconv_nparts(Ln)
+
+    @staticmethod
+    def dw_fwd(src, conv, out, part, k, s, Lo, NP, N):
+        check(L.lib().trunet_dwconv_fwd(ptr(src.t), ptr(src.bn.scale), ptr(src.bn.shift), ptr(conv.weight.data),
+                                        ptr(conv.bias.data), ptr(out), ptr(part), conv.out_channels, k, s, src.L, Lo, NP,
+                                        N, L.stream()), "dwconv_fwd")
+
+    @staticmethod
+    def dw_bwd(dy, z, bn, a_pw, dwc, dy_pw, part, wpart, bpart, k, s_, Lo, NP, N):
+        lib = L.lib()
+        tail = (ptr(bn.ca), ptr(bn.cb), ptr(bn.cc), ptr(a_pw.t), ptr(a_pw.bn.scale), ptr(a_pw.bn.shift), ptr(a_pw.bn.mean),
+                ptr(dwc.weight.data), ptr(dy_pw), ptr(part), ptr(wpart), ptr(bpart), dwc.out_channels, k, s_, a_pw.L, Lo,
+                NP, N, L.stream())
+        # z (the depthwise conv's own output) is recomputed from its input rows instead of read: one row pass less
+        rc = lib.trunet_dwconv_bwd_rz(ptr(dy), ptr(dwc.bias.data), *tail) if DW_RZ else L.TRUNET_ENOTSUP
+        if rc == L.TRUNET_ENOTSUP:
+            rc = lib.trunet_dwconv_bwd(ptr(dy), ptr(z), *tail)
+        check(rc, "dwconv_bwd")
+
+
 class TRUNetEngine:
     # (kernel, stride) of the depthwise convs of encoder.1..5 and of the transposed convs of decoder.0..5
     ENC = [(3, 1), (5, 2), (3, 1), (5, 2), (3, 2)]
@@ -203,6 +442,7 @@ class TRUNetEngine:
     def __init__(self, net):
         self.net = net
         self._ws = {}
+        self.f32 = Fp32Kernels(self)
 
     # ------------------------------------------------------------------ helpers
     def ws(self, NP, dev, record=False):
@@ -223,57 +463,17 @@ class TRUNetEngine:
                 "the same module ran before this backward (forward #%d, workspace is at #%d).  Call backward() before "
                 "the next training forward (no_grad / eval forwards in between are fine)." % (gen, w.gen))
 
-    def _gemm(self, w, *, N, NP, P, M, out, out_L, W, ldw_m, ldw_c, segs, p_begin=0, out_pos_off=0, m_out_off=0,
-              w_m_off=0, epi=0, bias=None, zmask=None, e0=None, e1=None, e2=None, stats=None):
-        a = GemmArgs()
-        a.NP, a.N, a.P, a.p_begin = NP, N, P, p_begin
-        a.M, a.m_out_off, a.out_L, a.out_pos_off = M, m_out_off, out_L, out_pos_off
-        a.ldw_m, a.ldw_c, a.w_m_off = ldw_m, ldw_c, w_m_off
-        a.nseg = len(segs)
-        for i, s in enumerate(segs):
-            a.seg[i] = s
-        a.out, a.W = ptr(out), ptr(W)
-        if bias is not None:
-            epi |= EPI_BIAS
-            a.bias = ptr(bias)
-        if zmask is not None:
-            epi |= EPI_MASK
-            a.zmask, a.e0, a.e1, a.e2 = ptr(zmask), ptr(e0), ptr(e1), ptr(e2)
-        nparts = 0
-        if stats is not None:
-            epi |= EPI_STATS
-            nparts = L.lib().trunet_conv_gemm_nparts(M)
-            part = w.flat("partials", nparts * stats * 2, zero=True)
-            a.partials, a.M_stat = ptr(part), stats
-            if w.take_clean("partials"):
-                epi |= EPI_PREZERO
-        a.epi = epi
-        if PROFILE is not None:
-            fl = 2.0 * N * M * sum(s.nchan * _seg_positions(s, p_begin, P) for s in segs)
-            tag = "M%d K%s P%d%s%s" % (M, "+".join(str(s.nchan) for s in segs), P,
-                                       " two" if any(s.mode == PRO_BNBWD for s in segs) else "",
-                                       " mask" if zmask is not None else "")
-            with _Timed(_gemm_kernel_name(a), fl, tag):
-                check(L.lib().trunet_conv_gemm(a, L.stream()), "conv_gemm")
-            return nparts
-        check(L.lib().trunet_conv_gemm(a, L.stream()), "conv_gemm")
-        return nparts
+    def _fam(self, act):
+        """the kernel family of the layer that reads activation `act`"""
+        return self.f32
 
-    def _gemm_args(self, *, N, NP, P, M, out, out_L, W, ldw_m, ldw_c, segs, bias=None, p_begin=0):
+    def _gemm(self, w, **kw):
+        """trunet_conv_gemm (Fp32Kernels.gemm); returns the number of statistics partial images"""
+        return self.f32.gemm(w, **kw)
+
+    def _gemm_args(self, **kw):
         """GemmArgs for a launch that is repeated with a changing segment offset (the TGRU time loop)."""
-        a = GemmArgs()
-        a.NP, a.N, a.P, a.p_begin = NP, N, P, p_begin
-        a.M, a.m_out_off, a.out_L, a.out_pos_off = M, 0, out_L, 0
-        a.ldw_m, a.ldw_c, a.w_m_off = ldw_m, ldw_c, 0
-        a.nseg = len(segs)
-        for i, sg in enumerate(segs):
-            a.seg[i] = sg
-        a.out, a.W = ptr(out), ptr(W)
-        a.epi = 0
-        if bias is not None:
-            a.epi |= EPI_BIAS
-            a.bias = ptr(bias)
-        return a
+        return self.f32.gemm_args(**kw)
 
     # ------------------------------------------------------------------ TGRU as a trained layer (use_tgru)
     def _tgru_block(self):
@@ -356,8 +556,8 @@ class TRUNetEngine:
         # pointwise conv + BatchNorm backward (fused): weight/bias gradient and dL/dh_t at position t+1
         dhs = w.get("tg.dhs", (Hh, T + 1, SP))
         dhs[:, 0].zero_()
-        self._pw_bwd(w, N=S, NP=SP, P=T, M=Cc, dz=dys, dz1=zc, dz_bn=bn, W=conv.weight, bias=conv.bias,
-                     segs=[make_seg(hs, Hh, T + 1, pos_off=1)], outs=[dict(out=dhs)], grads=grads)
+        self._pw_bwd(w, self.f32, N=S, NP=SP, P=T, M=Cc, dz=dys, dz1=zc, dz_bn=bn, W=conv.weight, bias=conv.bias,
+                     segs=[make_seg(hs, Hh, T + 1, pos_off=1)], outs=[dict(out=dhs)], grads=grads, fused=True)
         # backward through time
         dgi = w.get("tg.dgi", (3 * Hh, T, SP))
         dgh = w.get("tg.dgh", (3 * Hh, T, SP))
@@ -378,12 +578,12 @@ class TRUNetEngine:
                     carry = cg
         # weight gradients over all time steps at once (384 rows of dz in three launches of 128)
         for g in range(3):
-            self._wgrad(w, N=S, NP=SP, P=T, M=Hh, dz=dgh, dz_L=T, dz_bn=None, a_m_off=g * Hh, w_m_off=g * Hh,
-                        W=gru.weight_hh_l0, ldw_m=Hh, ldw_c=1, segs=[make_seg(hs, Hh, T + 1)], grads=grads,
-                        bias=gru.bias_hh_l0, b_off=g * Hh)
-            self._wgrad(w, N=S, NP=SP, P=T, M=Hh, dz=dgi, dz_L=T, dz_bn=None, a_m_off=g * Hh, w_m_off=g * Hh,
-                        W=gru.weight_ih_l0, ldw_m=C, ldw_c=1, segs=[make_seg(xs, C, T)], grads=grads,
-                        bias=gru.bias_ih_l0, b_off=g * Hh)
+            self.f32.wgrad(w, N=S, NP=SP, P=T, M=Hh, dz=dgh, dz_L=T, dz_bn=None, a_m_off=g * Hh, w_m_off=g * Hh,
+                           W=gru.weight_hh_l0, ldw_m=Hh, ldw_c=1, segs=[make_seg(hs, Hh, T + 1)], grads=grads,
+                           bias=gru.bias_hh_l0, b_off=g * Hh)
+            self.f32.wgrad(w, N=S, NP=SP, P=T, M=Hh, dz=dgi, dz_L=T, dz_bn=None, a_m_off=g * Hh, w_m_off=g * Hh,
+                           W=gru.weight_ih_l0, ldw_m=C, ldw_c=1, segs=[make_seg(xs, C, T)], grads=grads,
+                           bias=gru.bias_ih_l0, b_off=g * Hh)
         # data gradient of the input projection, back to frames-last through FGRU's BatchNorm+ReLU
         dxs = w.get("tg.dxs", (C, T, SP))
         self._gemm(w, N=S, NP=SP, P=T, M=C, out=dxs, out_L=T, W=gru.weight_ih_l0.data, ldw_m=1, ldw_c=C,
@@ -402,12 +602,12 @@ class TRUNetEngine:
         self._bn_bwd(w, src.bn, nparts, grads, part_name="tg.partials")
         return dyf, src.t, src.bn
 
-    def _bn_fwd(self, w, name, module, C, count, nparts, training):
+    def _bn_fwd(self, w, name, module, C, count, nparts, training, part_name="partials"):
         st = w.bn(name, C)
         st.module, st.count = module, float(count)
         lib = L.lib()
         if training:
-            part = w.flat("partials", nparts * C * 2, zero=True)
+            part = w.flat(part_name, nparts * C * 2, zero=True)
             L.bump_mutation_epoch()     # running statistics are written through raw pointers
             rm = module.running_mean if module.track_running_stats else None
             rv = module.running_var if module.track_running_stats else None
@@ -417,7 +617,7 @@ class TRUNetEngine:
                                              ptr(module.bias.data), module.eps, mom, ptr(rm), ptr(rv),
                                              ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.rstd), nbt, L.stream()),
                   "bn_finalize_fwd")
-            w.pending.discard("partials")
+            w.pending.discard(part_name)
         else:
             check(lib.trunet_bn_eval_affine(C, ptr(module.weight.data), ptr(module.bias.data),
                                             ptr(module.running_mean), ptr(module.running_var), module.eps,
@@ -427,61 +627,43 @@ class TRUNetEngine:
     def _pw(self, w, name, srcs, conv, bn, N, NP, training, x1_left=0):
         """Conv1d(k=1) over one or two concatenated sources (+BN statistics).  srcs[0] may be
         shorter/longer than the output length (F.pad / crop by ``x1_left``, network.py:96-98)."""
+        fam = self._fam(srcs[-1])
         Ln = srcs[-1].L
-        Co = conv.out_channels
-        K = conv.in_channels
-        out = w.get("z:" + name, (Co, Ln, NP))
+        Co, K = conv.out_channels, conv.in_channels
+        out = fam.alloc(w, "z:" + name, Co, Ln, NP)
         segs, off = [], 0
         for i, s in enumerate(srcs):
             segs.append(s.seg(pos_off=(-x1_left if (i == 0 and len(srcs) == 2) else 0), woff=off))
             off += s.C
         assert off == K
-        nparts = self._gemm(w, N=N, NP=NP, P=Ln, M=Co, out=out, out_L=Ln, W=conv.weight.data, ldw_m=K, ldw_c=1,
-                            segs=segs, bias=conv.bias.data, stats=(Co if (bn is not None and training) else None))
+        nparts = fam.gemm(w, N=N, NP=NP, P=Ln, M=Co, out=out, out_L=Ln, W=conv.weight.data, ldw_m=K, ldw_c=1,
+                          segs=segs, bias=conv.bias.data, stats=(Co if (bn is not None and training) else None))
         st = self._bn_fwd(w, name, bn, Co, N * Ln, nparts, training) if bn is not None else None
-        return Act(out, Co, Ln, st)
+        return fam.Act(out, Co, Ln, st)
 
     def _convT(self, w, name, src, conv, bn, N, NP, training):
-        k, s = conv.kernel_size[0], conv.stride[0]
-        pad = conv.padding[0]
-        Ci, Co = conv.in_channels, conv.out_channels
+        fam = self._fam(src)
+        k, s, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        Co = conv.out_channels
         Lo = (src.L - 1) * s - 2 * pad + k
-        out = w.get("z:" + name, (Co, Lo, NP))
+        out = fam.alloc(w, "z:" + name, Co, Lo, NP)
         segs = [src.seg(pos_off=pad - kk, woff=kk, pos_div=s) for kk in range(k)]
-        nparts = self._gemm(w, N=N, NP=NP, P=Lo, M=Co, out=out, out_L=Lo, W=conv.weight.data, ldw_m=k,
-                            ldw_c=Co * k, segs=segs, bias=conv.bias.data,
-                            stats=(Co if (bn is not None and training) else None))
+        nparts = fam.gemm(w, N=N, NP=NP, P=Lo, M=Co, out=out, out_L=Lo, W=conv.weight.data, ldw_m=k, ldw_c=Co * k,
+                          segs=segs, bias=conv.bias.data, stats=(Co if (bn is not None and training) else None))
         st = self._bn_fwd(w, name, bn, Co, N * Lo, nparts, training) if bn is not None else None
-        return Act(out, Co, Lo, st)
+        return fam.Act(out, Co, Lo, st)
 
     def _dw(self, w, name, src, conv, bn, N, NP, training):
+        fam = self._fam(src)
         k, s = conv.kernel_size[0], conv.stride[0]
         C = conv.out_channels
         Lo = (src.L + 2 * (k // 2) - k) // s + 1
-        out = w.get("z:" + name, (C, Lo, NP))
-        lib = L.lib()
-        nparts = lib.trunet_dwconv_nparts(Lo)
-        part = w.flat("partials_dw", nparts * C * 2)
-        check(lib.trunet_dwconv_fwd(ptr(src.t), ptr(src.bn.scale), ptr(src.bn.shift), ptr(conv.weight.data),
-                                    ptr(conv.bias.data), ptr(out), ptr(part), C, k, s, src.L, Lo, NP, N,
-                                    L.stream()), "dwconv_fwd")
-        st = w.bn(name, C)
-        st.module, st.count = bn, float(N * Lo)
-        if training:
-            L.bump_mutation_epoch()     # running statistics are written through raw pointers
-            rm = bn.running_mean if bn.track_running_stats else None
-            rv = bn.running_var if bn.track_running_stats else None
-            mom = BN_MOM if bn.momentum is None else bn.momentum
-            nbt = bn.num_batches_tracked.data_ptr() if bn.track_running_stats else None
-            check(lib.trunet_bn_finalize_fwd(ptr(part), nparts, C, float(N * Lo), ptr(bn.weight.data),
-                                             ptr(bn.bias.data), bn.eps, mom, ptr(rm), ptr(rv), ptr(st.scale),
-                                             ptr(st.shift), ptr(st.mean), ptr(st.rstd), nbt, L.stream()), "bn_finalize_fwd")
-        else:
-            check(lib.trunet_bn_eval_affine(C, ptr(bn.weight.data), ptr(bn.bias.data), ptr(bn.running_mean),
-                                            ptr(bn.running_var), bn.eps, ptr(st.scale), ptr(st.shift), L.stream()),
-                  "bn_eval_affine")
-        return Act(out, C, Lo, st)
-
+        out = fam.alloc(w, "z:" + name, C, Lo, NP)
+        nparts = fam.dw_nparts(NP, Lo, bwd=False)
+        part = w.flat("partials_dw", nparts * C * 2)        # every row is written by the launch: no zero-fill, never pending
+        fam.dw_fwd(src, conv, out, part, k, s, Lo, NP, N)
+        st = self._bn_fwd(w, name, bn, C, N * Lo, nparts, training, part_name="partials_dw")
+        return fam.Act(out, C, Lo, st)
 
     # ------------------------------------------------------------------ stand-alone blocks (network.py:9-120)
     def _load(self, w, name, x):
@@ -795,116 +977,20 @@ class TRUNetEngine:
         if len(self._wg_touched) == len(self._wg_layout):
             L.register_flat_grad(flat, {id(p): o for p, o in self._wg_layout.items()}, self._wg_total)
 
-    def _wgrad(self, w, *, N, NP, P, M, dz, dz_L, dz_bn, W, ldw_m, ldw_c, segs, grads, bias=None, a_pos_off=0,
-               a_m_off=0, w_m_off=0, b_off=0, dz1=None):
-        lib = L.lib()
-        a = WgradArgs()
-        a.NP, a.N, a.P, a.p_begin = NP, N, P, 0
-        a.M, a.a_L, a.a_pos_off, a.a_m_off = M, dz_L, a_pos_off, a_m_off
-        a.ldw_m, a.ldw_c, a.w_m_off = ldw_m, ldw_c, w_m_off
-        a.nseg = len(segs)
-        for i, s in enumerate(segs):
-            a.seg[i] = s
-        a.a0 = ptr(dz)
-        if dz_bn is not None:
-            if dz1 is None:
-                raise L.TrunetHipError("weight gradient behind a BatchNorm needs the raw conv output next to dy")
-            a.a_mode = PRO_BNBWD
-            a.a1, a.ac0, a.ac1, a.ac2 = ptr(dz1), ptr(dz_bn.ca), ptr(dz_bn.cb), ptr(dz_bn.cc)
-        else:
-            a.a_mode = PRO_NONE
-        a.w_numel = self._wg_total                      # image stride of the shared buffer
-        a.w_partials = self._wg_slot(W)
-        if bias is not None:
-            a.b_partials = self._wg_slot(bias)
-            a.b_stride, a.b_off = self._wg_total, b_off
-        if PROFILE is not None:
-            fl = 2.0 * N * M * sum(s.nchan * _seg_positions(s, 0, P) for s in segs)
-            with _Timed("conv_wgrad_kernel<%s>" % ("true" if dz_bn is not None else "false"), fl,
-                        "M%d K%s P%d" % (M, "+".join(str(s.nchan) for s in segs), P)):
-                check(lib.trunet_conv_wgrad(a, L.stream()), "conv_wgrad")
-        else:
-            check(lib.trunet_conv_wgrad(a, L.stream()), "conv_wgrad")
-
-    @staticmethod
-    def _dz_seg(dy_, z_, bn_, C, Ln, **kw):
-        if bn_ is None:
-            return make_seg(dy_, C, Ln, mode=PRO_NONE, **kw)
-        return make_seg(dy_, C, Ln, mode=PRO_BNBWD, src1=z_, c0=bn_.ca, c1=bn_.cb, c2=bn_.cc, **kw)
-
-    def _pw_bwd(self, w, *, N, NP, P, M, dz, dz1, dz_bn, W, bias, segs, outs, grads, fused=True, a_m_off=0, w_m_off=0,
-                b_off=0, must_fuse=False):
+    def _pw_bwd(self, w, fam, *, N, NP, P, M, dz, dz1, dz_bn, W, bias, segs, outs, grads, fused=None, **rows):
         """Backward of a Conv1d(k=1)+BatchNorm layer: weight/bias gradient and, per source segment, the data gradient with
         its ReLU mask / skip accumulation / BatchNorm-backward statistics.
         outs[i] = dict(out=tensor, src=Act or None (mask, + statistics when src.bn), accum=bool).
-        One fused launch (trunet_pw_bwd) when the kernel supports the shape, else (TRUNET_ENOTSUP: e.g. tensors beyond
-        its 32-bit row offsets, thin layers) trunet_conv_wgrad + one trunet_conv_gemm per source."""
-        lib = L.lib()
+        One fused launch (fam.pw_bwd) when ``fused`` (default: the family's switch) and the kernel takes the shape, else
+        one weight-gradient launch + one GEMM per source.  rows: a_m_off / w_m_off / b_off / must_fuse of Fp32Kernels.pw_bwd."""
         K = sum(s.nchan for s in segs)
-        if fused:
-            a = PwBwdArgs()
-            aw = a.w
-            aw.NP, aw.N, aw.P, aw.p_begin = NP, N, P, 0
-            # a_m_off / w_m_off / b_off: a ROW BLOCK of a wider layer (the GRU input projection, 2 x 192 rows, as blocks of
-            # 128 + 64): first dz row, first weight row inside W, first bias row
-            aw.M, aw.a_L, aw.a_pos_off, aw.a_m_off = M, P, 0, a_m_off
-            aw.ldw_m, aw.ldw_c, aw.w_m_off = K, 1, w_m_off
-            aw.nseg = len(segs)
-            aw.a0, aw.a1 = ptr(dz), ptr(dz1)
-            aw.a_mode = PRO_BNBWD
-            aw.ac0, aw.ac1, aw.ac2 = ptr(dz_bn.ca), ptr(dz_bn.cb), ptr(dz_bn.cc)
-            aw.w_numel = self._wg_total                     # image stride of the shared buffer
-            aw.w_partials, aw.b_partials = self._wg_slot(W), self._wg_slot(bias)
-            aw.b_stride, aw.b_off = self._wg_total, b_off
-            a.W = ptr(W.data)
-            nparts = lib.trunet_pw_bwd_nparts()
-            stat_parts = []
-            for i, (sg, o) in enumerate(zip(segs, outs)):
-                aw.seg[i] = sg
-                d = a.dg[i]
-                d.out = ptr(o["out"])
-                fl = DG_STORE
-                src = o.get("src")
-                if src is not None:
-                    fl |= DG_MASK
-                    d.zmask = ptr(src.t)
-                    if src.bn is not None:
-                        fl |= DG_STATS
-                        part = w.flat("pwb_partials%d" % i, nparts * sg.nchan * 2, zero=True)
-                        d.e2, d.partials = ptr(src.bn.mean), ptr(part)
-                        stat_parts.append((src.bn, "pwb_partials%d" % i))
-                        if w.take_clean("pwb_partials%d" % i):
-                            fl |= DG_PREZERO
-                if o.get("accum"):
-                    fl |= DG_ACCUM
-                d.flags = fl
-            if PROFILE is not None:
-                fl_ = 4.0 * N * M * sum(s.nchan * _seg_positions(s, 0, P) for s in segs)
-                # the instance trunet_pw_bwd launches, as rocprofv3 prints it: <AK, SEC, KSPLIT> (KSPLIT: two source row tiles)
-                ksplit = K == 64 and os.environ.get("TRUNET_PWB_KSPLIT", "1") != "0"
-                name = "pw_bwd_kernel<%d, %s, %s, %s>" % (16 if M <= 32 else (32 if M <= 64 else 64), "true" if K == 192 else "false",
-                                                          "true" if ksplit else "false",
-                                                          "true" if lib.trunet_gemm_x3_enable(-1) & L.X3_BWD else "false")
-                # algorithmic bytes: dy and z_y once, every source row once, every gradient row written once (read as well
-                # where it accumulates), fp32, valid frames only
-                by_ = 4.0 * N * (2 * M * P + sum((3 if o.get("accum") else 2) * s.nchan * _seg_positions(s, 0, P)
-                                                 for s, o in zip(segs, outs)))
-                with _Timed(name, fl_, "M%d K%s P%d" % (M, "+".join(str(s.nchan) for s in segs), P), nbytes=by_):
-                    rc = lib.trunet_pw_bwd(a, L.stream())
-            else:
-                rc = lib.trunet_pw_bwd(a, L.stream())
-            if rc == 0:
-                for bn, pname in stat_parts:
-                    self._bn_bwd(w, bn, nparts, grads, part_name=pname)
-                return
-            for _, pname in stat_parts:          # nothing was launched: the statistics buffers are as clean as before
-                w.pending.discard(pname)
-            if rc != L.TRUNET_ENOTSUP or must_fuse:
-                check(rc, "pw_bwd")
-        assert not (a_m_off or w_m_off or b_off), "row blocks exist on the fused kernel only"
-        # ---- separate launches
-        self._wgrad(w, N=N, NP=NP, P=P, M=M, dz=dz, dz1=dz1, dz_L=P, dz_bn=dz_bn, W=W, ldw_m=K, ldw_c=1, segs=segs,
-                    grads=grads, bias=bias)
+        if fused is None:
+            fused = fam.fuse_pw()
+        if fused and fam.pw_bwd(w, N, NP, P, M, dz, dz1, dz_bn, W, bias, segs, outs, grads, K, **rows):
+            return
+        assert not (rows.get("a_m_off") or rows.get("w_m_off") or rows.get("b_off")), "row blocks exist on the fused kernel only"
+        fam.wgrad(w, N=N, NP=NP, P=P, M=M, dz=dz, dz1=dz1, dz_L=P, dz_bn=dz_bn, W=W, ldw_m=K, ldw_c=1, segs=segs,
+                  grads=grads, bias=bias)
         for sg, o in zip(segs, outs):
             src = o.get("src")
             p0, p1 = max(0, -sg.pos_off), min(P, sg.L - sg.pos_off)
@@ -918,9 +1004,9 @@ class TRUNetEngine:
                     one.fill_(1.0)
                     zero.zero_()
                     kw = dict(zmask=src.t, e0=one, e1=zero, e2=zero)
-            nparts = self._gemm(w, N=N, NP=NP, P=p1 - p0, p_begin=p0, M=sg.nchan, out=o["out"], out_L=sg.L,
-                                out_pos_off=sg.pos_off, W=W.data, ldw_m=1, ldw_c=K, w_m_off=sg.woff,
-                                segs=[self._dz_seg(dz, dz1, dz_bn, M, P)], epi=(EPI_ACCUM if o.get("accum") else 0), **kw)
+            nparts = fam.gemm(w, N=N, NP=NP, P=p1 - p0, p_begin=p0, M=sg.nchan, out=o["out"], out_L=sg.L,
+                              out_pos_off=sg.pos_off, W=W.data, ldw_m=1, ldw_c=K, w_m_off=sg.woff,
+                              segs=[fam.dz_seg(dz, dz1, dz_bn, M, P)], epi=(EPI_ACCUM if o.get("accum") else 0), **kw)
             if src is not None and src.bn is not None:
                 self._bn_bwd(w, src.bn, nparts, grads)
 
@@ -929,25 +1015,34 @@ class TRUNetEngine:
     # gradient of the raw output itself).  Sources are Acts: with a BatchNorm state the data gradient is masked and its
     # BatchNorm-backward sums are reduced ("bn"); ``*_relu`` marks a ReLU-only source (enc0); a raw source (block
     # inputs, skip tensors) gets the plain gradient.
-    def _bwd_tr(self, w, N, NP, ct, pw, a_pw, Lo, up, x1, x1_mask, skip, left, dy_x1, g_skip, dy_pw_name, grads):
-        """FirstTrCNN / TrCNN / LastTrCNN (network.py:60-120): transposed conv, then the pointwise conv over
-        [x1 (padded / cropped by ``left``) | skip].  x1_mask: x1 itself when its BatchNorm+ReLU sits between x1 and this
-        block (full network), None for a raw block input."""
+    def _bwd_convT(self, w, N, NP, ct, a_pw, Lo, up, dy_pw_name, grads):
+        """ConvTranspose1d (+BatchNorm) that reads a_pw: weight / bias gradient and the masked data gradient at a_pw's
+        BatchNorm output with its BatchNorm-backward sums, in a_pw's kernel family.  Returns that gradient."""
+        fam = self._fam(a_pw)
         dy, z, bn = up
         k, s_, pad = ct.kernel_size[0], ct.stride[0], ct.padding[0]
         Ci, Co = ct.in_channels, ct.out_channels
-        dy_pw = w.get(dy_pw_name, (Ci, a_pw.L, NP))
-        if not (FUSED_CONVT and bn is not None and self._convt_bwd(w, N, NP, ct, a_pw, Lo, dy, z, bn, dy_pw, grads)):
-            # transposed conv: weight/bias gradient
-            self._wgrad(w, N=N, NP=NP, P=Lo, M=Co, dz=dy, dz1=z, dz_L=Lo, dz_bn=bn, W=ct.weight, ldw_m=k,
-                        ldw_c=Co * k, segs=[a_pw.seg(pos_off=pad - kk, woff=kk, pos_div=s_) for kk in range(k)],
-                        grads=grads, bias=ct.bias)
-            # transposed conv: data gradient -> dy of the pw BN (+ stats)
-            segs = [self._dz_seg(dy, z, bn, Co, Lo, pos_mul=s_, pos_off=kk - pad, woff=kk) for kk in range(k)]
-            nparts = self._gemm(w, N=N, NP=NP, P=a_pw.L, M=Ci, out=dy_pw, out_L=a_pw.L, W=ct.weight.data,
-                                ldw_m=Co * k, ldw_c=k, segs=segs, zmask=a_pw.t, e0=a_pw.bn.scale, e1=a_pw.bn.shift,
-                                e2=a_pw.bn.mean, stats=Ci)
+        dy_pw = fam.alloc(w, dy_pw_name, Ci, a_pw.L, NP)
+        if not (bn is not None and fam.convt_bwd(w, N, NP, ct, a_pw, Lo, dy, z, bn, dy_pw, grads)):
+            fam.wgrad(w, N=N, NP=NP, P=Lo, M=Co, dz=dy, dz1=z, dz_L=Lo, dz_bn=bn, W=ct.weight, ldw_m=k, ldw_c=Co * k,
+                      segs=[a_pw.seg(pos_off=pad - kk, woff=kk, pos_div=s_) for kk in range(k)], grads=grads,
+                      bias=ct.bias)
+            segs = [fam.dz_seg(dy, z, bn, Co, Lo, pos_mul=s_, pos_off=kk - pad, woff=kk) for kk in range(k)]
+            nparts = fam.gemm(w, N=N, NP=NP, P=a_pw.L, M=Ci, out=dy_pw, out_L=a_pw.L, W=ct.weight.data, ldw_m=Co * k,
+                              ldw_c=k, segs=segs, zmask=a_pw.t, e0=a_pw.bn.scale, e1=a_pw.bn.shift, e2=a_pw.bn.mean,
+                              stats=Ci)
             self._bn_bwd(w, a_pw.bn, nparts, grads)
+        return dy_pw
+
+    def _bwd_tr(self, w, N, NP, ct, pw, a_pw, Lo, up, x1, x1_mask, skip, left, dy_x1, g_skip, dy_pw_name, grads,
+                dy_pw=None):
+        """FirstTrCNN / TrCNN / LastTrCNN (network.py:60-120): transposed conv, then the pointwise conv over
+        [x1 (padded / cropped by ``left``) | skip].  x1_mask: x1 itself when its BatchNorm+ReLU sits between x1 and this
+        block (full network), None for a raw block input.  dy_pw: given when the caller has run the transposed conv's
+        part itself (``_bwd_convT`` in another kernel family)."""
+        fam = self._fam(a_pw)
+        if dy_pw is None:
+            dy_pw = self._bwd_convT(w, N, NP, ct, a_pw, Lo, up, dy_pw_name, grads)
         # pointwise conv over [x1 | skip]
         Lp = a_pw.L
         srcs = [x1.seg(pos_off=-left, woff=0)] + ([skip.seg(woff=x1.C)] if skip is not None else [])
@@ -955,51 +1050,14 @@ class TRUNetEngine:
         if p1 - p0 < x1.L:          # cropped positions of x1 (network.py:96-97 with a negative pad) get no gradient
             w.zero_crop(dy_x1, p0 - left, p1 - left)
         outs = [dict(out=dy_x1, src=x1_mask)] + ([dict(out=g_skip)] if skip is not None else [])
-        # decoder.5's 8-row layer: trunet_pw_bwd pads its dz block to one 32-row MFMA tile (round 3; TRUNET_FUSED_THIN=0
-        # keeps the three separate launches of rounds 1-2: conv_wgrad + two conv_gemm, 1.36 ms)
-        fused = FUSED_PWBWD and (pw.out_channels % 32 == 0 or (pw.out_channels <= 32 and FUSED_THIN))
-        self._pw_bwd(w, N=N, NP=NP, P=Lp, M=pw.out_channels, dz=dy_pw, dz1=a_pw.t, dz_bn=a_pw.bn, W=pw.weight,
-                     bias=pw.bias, segs=srcs, outs=outs, grads=grads, fused=fused)
-
-    def _convt_bwd(self, w, N, NP, ct, a_pw, Lo, dy, z, bn, dy_pw, grads):
-        """Fused backward of ConvTranspose1d(64 -> 64) + BatchNorm (trunet_convt_bwd): weight / bias gradient, the data
-        gradient at the pointwise BatchNorm's output (masked) and its BatchNorm-backward sums in one pass over (dy, z,
-        source).  False when the kernel does not support the layer (TRUNET_ENOTSUP): the caller takes the separate launches."""
-        lib = L.lib()
-        k, s_, pad = ct.kernel_size[0], ct.stride[0], ct.padding[0]
-        a = ConvtBwdArgs()
-        a.NP, a.N, a.Lin, a.Lout, a.K, a.S, a.pad = NP, N, a_pw.L, Lo, k, s_, pad
-        a.Ci, a.Co = ct.in_channels, ct.out_channels
-        if a.Ci != 64 or a.Co != 64:
-            return False
-        nparts = lib.trunet_convt_bwd_nparts()
-        part = w.flat("ct_partials", nparts * a.Ci * 2)
-        a.dy, a.z = ptr(dy), ptr(z)
-        a.ca, a.cb, a.cc = ptr(bn.ca), ptr(bn.cb), ptr(bn.cc)
-        a.src, a.s_scale, a.s_shift, a.s_mean = ptr(a_pw.t), ptr(a_pw.bn.scale), ptr(a_pw.bn.shift), ptr(a_pw.bn.mean)
-        a.W, a.dsrc, a.partials = ptr(ct.weight.data), ptr(dy_pw), ptr(part)
-        a.w_numel = self._wg_total
-        a.w_partials, a.b_partials = self._wg_slot(ct.weight), self._wg_slot(ct.bias)
-        a.b_stride, a.b_off = self._wg_total, 0
-        if PROFILE is not None:
-            fl = 4.0 * N * a.Ci * a.Co * sum(1 for q in range(a_pw.L) for kk in range(k) if 0 <= q * s_ - pad + kk < Lo)
-            x3 = lib.trunet_gemm_x3_enable(-1) & L.X3_BWD
-            with _Timed("convt_bwd_kernel<%d, %d, %s>" % (k, s_, "true" if x3 else "false"), fl, "L%d" % a_pw.L):
-                rc = lib.trunet_convt_bwd(a, L.stream())
-        else:
-            rc = lib.trunet_convt_bwd(a, L.stream())
-        if rc == L.TRUNET_ENOTSUP:
-            return False
-        check(rc, "convt_bwd")
-        self._bn_bwd(w, a_pw.bn, nparts, grads, part_name="ct_partials")
-        return True
+        self._pw_bwd(w, fam, N=N, NP=NP, P=Lp, M=pw.out_channels, dz=dy_pw, dz1=a_pw.t, dz_bn=a_pw.bn, W=pw.weight,
+                     bias=pw.bias, segs=srcs, outs=outs, grads=grads, fused=fam.fuse_pw(pw.out_channels))
 
     def _ident_bnbwd(self, w, C):
         """(ca, cb, cc) = (1, 0, 0): a dz operand that is already the gradient of the raw output, for kernels whose dz
         prologue is the BatchNorm backward ca dy + cb z + cc"""
         t = w.t.get("ident_bnbwd%d" % C)
         if t is None:
-            import types
             ca = torch.ones(C, device=self._wg_base.device, dtype=torch.float32)
             zz = torch.zeros(C, device=self._wg_base.device, dtype=torch.float32)
             t = w.t["ident_bnbwd%d" % C] = types.SimpleNamespace(ca=ca, cb=zz, cc=zz.clone())
@@ -1013,15 +1071,15 @@ class TRUNetEngine:
         conv, gru = blk.conv[0], blk.GRU
         Hh, Lg = gru.hidden_size, hout.L
         dhout = w.get("dhout", (2 * Hh, Lg, NP))
-        self._pw_bwd(w, N=N, NP=NP, P=Lg, M=conv.out_channels, dz=dy, dz1=z, dz_bn=bn, W=conv.weight,
-                     bias=conv.bias, segs=[hout.seg()], outs=[dict(out=dhout)], grads=grads, fused=FUSED_PWBWD)
+        self._pw_bwd(w, self.f32, N=N, NP=NP, P=Lg, M=conv.out_channels, dz=dy, dz1=z, dz_bn=bn, W=conv.weight,
+                     bias=conv.bias, segs=[hout.seg()], outs=[dict(out=dhout)], grads=grads)
         # -------- GRU recurrence backward
         dgi = w.get("dgi", (6 * Hh, Lg, NP))
         dghn = w.get("dghn", (2 * Hh, Lg, NP))
         gates = w.t["gates"]
         check(lib.trunet_gru_bwd(ptr(dhout), ptr(hout.t), ptr(gates), ptr(gru.weight_hh_l0.data),
                                  ptr(gru.weight_hh_l0_reverse.data), ptr(dgi), ptr(dghn), Hh, Lg, NP, N, st), "gru_bwd")
-        # (TRUNET_FUSED_GRU_PROJ=0: conv_wgrad + conv_gemm for the projection, rounds 1-2)
+        # (TRUNET_FUSED_GRU_PROJ=0: conv_wgrad + conv_gemm for the projection)
         fuse_proj = (FUSED_PWBWD and FUSED_GRU_PROJ and src_mask is not None and src_mask.bn is not None and
                      src_mask.t is src.t and 3 * Hh > 128 and (3 * Hh - 128) % 32 == 0 and gru.input_size % 32 == 0)
         for d, sfx in enumerate(("", "_reverse")):
@@ -1031,15 +1089,15 @@ class TRUNetEngine:
             bih_p = getattr(gru, "bias_ih_l0" + sfx)
             hseg = make_seg(hout.t[d * Hh:(d + 1) * Hh], Hh, Lg, pos_off=(1 if d else -1))
             # rows 0..2H-1 (r, z) come from dgi, rows 2H..3H-1 (n) from dghn
-            self._wgrad(w, N=N, NP=NP, P=Lg, M=2 * Hh, dz=dgi, dz_L=Lg, dz_bn=None, a_m_off=d * 3 * Hh, W=whh,
-                        ldw_m=Hh, ldw_c=1, segs=[hseg], grads=grads, bias=bhh, b_off=0)
-            self._wgrad(w, N=N, NP=NP, P=Lg, M=Hh, dz=dghn, dz_L=Lg, dz_bn=None, a_m_off=d * Hh, w_m_off=2 * Hh,
-                        W=whh, ldw_m=Hh, ldw_c=1, segs=[hseg], grads=grads, bias=bhh, b_off=2 * Hh)
+            self.f32.wgrad(w, N=N, NP=NP, P=Lg, M=2 * Hh, dz=dgi, dz_L=Lg, dz_bn=None, a_m_off=d * 3 * Hh, W=whh,
+                           ldw_m=Hh, ldw_c=1, segs=[hseg], grads=grads, bias=bhh, b_off=0)
+            self.f32.wgrad(w, N=N, NP=NP, P=Lg, M=Hh, dz=dghn, dz_L=Lg, dz_bn=None, a_m_off=d * Hh, w_m_off=2 * Hh,
+                           W=whh, ldw_m=Hh, ldw_c=1, segs=[hseg], grads=grads, bias=bhh, b_off=2 * Hh)
             if fuse_proj:
                 continue
             # input projection weights: all 3H = 192 rows of dgi for this direction in one launch
-            self._wgrad(w, N=N, NP=NP, P=Lg, M=3 * Hh, dz=dgi, dz_L=Lg, dz_bn=None, a_m_off=d * 3 * Hh, W=wih_p,
-                        ldw_m=gru.input_size, ldw_c=1, segs=[src.seg()], grads=grads, bias=bih_p, b_off=0)
+            self.f32.wgrad(w, N=N, NP=NP, P=Lg, M=3 * Hh, dz=dgi, dz_L=Lg, dz_bn=None, a_m_off=d * 3 * Hh, W=wih_p,
+                           ldw_m=gru.input_size, ldw_c=1, segs=[src.seg()], grads=grads, bias=bih_p, b_off=0)
         if fuse_proj:
             # The input projection IS a pointwise layer (gi = W_ih a(src) + b_ih, 2 x 192 rows): its backward on the fused
             # kernel, one launch per row block (128 + 64 rows per direction; dz = dgi through the identity "BatchNorm
@@ -1054,7 +1112,7 @@ class TRUNetEngine:
                 sfx = "_reverse" if d else ""
                 last = i == len(blocks) - 1
                 o = dict(out=dy_src, src=(src_mask if last else Act(src_mask.t, src_mask.C, src_mask.L)), accum=i > 0)
-                self._pw_bwd(w, N=N, NP=NP, P=Lg, M=m, dz=dgi, dz1=dgi, dz_bn=ident, W=getattr(gru, "weight_ih_l0" + sfx),
+                self._pw_bwd(w, self.f32, N=N, NP=NP, P=Lg, M=m, dz=dgi, dz1=dgi, dz_bn=ident, W=getattr(gru, "weight_ih_l0" + sfx),
                              bias=getattr(gru, "bias_ih_l0" + sfx), segs=[src.seg()], outs=[o], grads=grads, fused=True,
                              a_m_off=d * 3 * Hh + r0, w_m_off=r0, b_off=r0, must_fuse=True)
             return
@@ -1072,53 +1130,56 @@ class TRUNetEngine:
         """DepthwiseSeparableConv1d (network.py:24-43): depthwise conv (fused dgrad + wgrad + BN-backward sums of the
         pointwise BatchNorm), then the pointwise conv; dy_prev receives the gradient of the block input ``prev``
         (added to the skip gradient already stored there when ``accum``)."""
+        fam = self._fam(a_pw)
         lib, st = L.lib(), L.stream()
         dy, z, bn = up
         pw, dwc = seq[0], seq[3]
         k, s_ = dwc.kernel_size[0], dwc.stride[0]
         C = dwc.out_channels
-        dy_pw = w.get(dy_pw_name, (C, a_pw.L, NP))
-        nparts = lib.trunet_dwconv_bwd_nparts(a_pw.L)
+        dy_pw = fam.alloc(w, dy_pw_name, C, a_pw.L, NP)
+        nparts = fam.dw_nparts(NP, a_pw.L, bwd=True)
         part = w.flat("partials_dw", nparts * C * 2)
         wpart = w.flat("dw_w_partials", nparts * C * k)
         bpart = w.flat("dw_b_partials", nparts * C)
-        tail = (ptr(bn.ca), ptr(bn.cb), ptr(bn.cc), ptr(a_pw.t), ptr(a_pw.bn.scale), ptr(a_pw.bn.shift), ptr(a_pw.bn.mean),
-                ptr(dwc.weight.data), ptr(dy_pw), ptr(part), ptr(wpart), ptr(bpart), C, k, s_, a_pw.L, a_dw.L, NP, N, st)
-        # z (the depthwise conv's own output) is recomputed from its input rows instead of read: one row pass less
-        rc = lib.trunet_dwconv_bwd_rz(ptr(dy), ptr(dwc.bias.data), *tail) if DW_RZ else L.TRUNET_ENOTSUP
-        if rc == L.TRUNET_ENOTSUP:
-            rc = lib.trunet_dwconv_bwd(ptr(dy), ptr(z), *tail)
-        check(rc, "dwconv_bwd")
+        fam.dw_bwd(dy, z, bn, a_pw, dwc, dy_pw, part, wpart, bpart, k, s_, a_dw.L, NP, N)
         check(lib.trunet_reduce_partials(self._wg_slot(dwc.weight), ptr(wpart), nparts, C * k, 0, st), "reduce")
         check(lib.trunet_reduce_partials(self._wg_slot(dwc.bias), ptr(bpart), nparts, C, 0, st), "reduce")
         self._bn_bwd(w, a_pw.bn, nparts, grads, part_name="partials_dw")
-        self._pw_bwd(w, N=N, NP=NP, P=a_pw.L, M=pw.out_channels, dz=dy_pw, dz1=a_pw.t, dz_bn=a_pw.bn, W=pw.weight,
-                     bias=pw.bias, segs=[prev.seg()], outs=[dict(out=dy_prev, src=prev_mask, accum=accum)],
-                     grads=grads, fused=FUSED_PWBWD)
+        self._pw_bwd(w, fam, N=N, NP=NP, P=a_pw.L, M=pw.out_channels, dz=dy_pw, dz1=a_pw.t, dz_bn=a_pw.bn, W=pw.weight,
+                     bias=pw.bias, segs=[prev.seg()], outs=[dict(out=dy_prev, src=prev_mask, accum=accum)], grads=grads)
 
     def _bwd_first(self, w, N, NP, c0, xa, dy, Lo, grads):
         """StandardConv1d (network.py:9-21): weight/bias gradient, one segment per tap of the input"""
         k, s_, pad = c0.kernel_size[0], c0.stride[0], c0.padding[0]
-        segs = [make_seg(xa.t, xa.C, xa.L, pos_mul=s_, pos_off=kk - pad, woff=kk) for kk in range(k)]
-        self._wgrad(w, N=N, NP=NP, P=Lo, M=c0.out_channels, dz=dy, dz_L=Lo, dz_bn=None, W=c0.weight,
-                    ldw_m=xa.C * k, ldw_c=k, segs=segs, grads=grads, bias=c0.bias)
+        segs = [xa.seg(pos_mul=s_, pos_off=kk - pad, woff=kk) for kk in range(k)]
+        self._fam(xa).wgrad(w, N=N, NP=NP, P=Lo, M=c0.out_channels, dz=dy, dz_L=Lo, dz_bn=None, W=c0.weight,
+                            ldw_m=xa.C * k, ldw_c=k, segs=segs, grads=grads, bias=c0.bias)
+
+    def _bwd_entry(self, w, acts, gout, N, NP, grads):
+        """The output cotangent (N, 8, 257) as the decoder's first upstream gradient (dy tensor, z tensor, BatchNorm state
+        of that z or None), and decoder.5's dy_pw when its transposed conv is already done here (else None)."""
+        last = acts["dec5"]
+        dyt = w.get("dy:dec5", (last.C, last.L, NP))
+        check(L.lib().trunet_to_frames_last(ptr(gout), ptr(dyt), N, last.C, last.L, NP, L.stream()), "to_frames_last")
+        return (dyt, last.t, None), None
+
+    def _bwd_bottleneck(self, w, acts, up, N, NP, grads):
+        """TGRU (when the forward ran it) and FGRU; returns the upstream gradient at enc5"""
+        if "tgru.ctx" in acts:            # time-recurrent block between FGRU and the decoder
+            up = self._tgru_seq_bwd(w, acts, up[0], up[2], N, NP, grads)
+        enc5 = acts["enc5"]
+        dy5 = w.get("dy:enc5", (enc5.C, enc5.L, NP))
+        self._bwd_fgru(w, N, NP, self.net.FGRU, up, acts["hout"], enc5, enc5, dy5, grads)
+        return dy5, enc5.t, enc5.bn
 
     def backward(self, ctx, gout):
         """gout: (N, 8, 257) cotangent.  Returns {parameter tensor: gradient}."""
         acts, N, NP, w, gen = ctx
         self._check_gen(w, gen)
         net = self.net
-        lib = L.lib()
-        st = L.stream()
         grads = {}
         self._wg_begin(w)
-        gout = gout.contiguous()
-        last = acts["dec5"]
-        dyt = w.get("dy:dec5", (last.C, last.L, NP))
-        check(lib.trunet_to_frames_last(ptr(gout), ptr(dyt), N, last.C, last.L, NP, st), "to_frames_last")
-
-        # current upstream gradient: (dy tensor, z tensor, BN state of that z or None)
-        up = (dyt, last.t, None)
+        up, dy_pw5 = self._bwd_entry(w, acts, gout.contiguous(), N, NP, grads)
         # -------- decoder, last to first
         for i in range(5, -1, -1):
             seq = (net.decoder[i].LastTrCNN if i == 5 else net.decoder[i].TrCNN) if i > 0 else net.decoder[0].FirstTrCNN
@@ -1126,28 +1187,21 @@ class TRUNetEngine:
                 x1, x1n = acts["dec%d" % (i - 1)], "dec%d" % (i - 1)
                 skip = acts["enc%d" % (5 - i)]
                 left = (skip.L - x1.L) // 2
-                g_skip = w.get("dy:enc%d" % (5 - i), (skip.C, skip.L, NP))
+                g_skip = self._fam(skip).alloc(w, "dy:enc%d" % (5 - i), skip.C, skip.L, NP)
             else:
                 x1n = "tgru" if "tgru" in acts else "fgru"
                 x1, skip, left, g_skip = acts[x1n], None, 0, None
-            dy_x1 = w.get("dy:" + x1n, (x1.C, x1.L, NP))
+            dy_x1 = self._fam(x1).alloc(w, "dy:" + x1n, x1.C, x1.L, NP)
             self._bwd_tr(w, N, NP, seq[3], seq[0], acts["dec%d.pw" % i], acts["dec%d" % i].L, up, x1, x1, skip, left,
-                         dy_x1, g_skip, "dy:dec%d.pw" % i, grads)
+                         dy_x1, g_skip, "dy:dec%d.pw" % i, grads, dy_pw=(dy_pw5 if i == 5 else None))
             up = (dy_x1, x1.t, x1.bn)
 
-        if "tgru.ctx" in acts:            # time-recurrent block between FGRU and the decoder
-            up = self._tgru_seq_bwd(w, acts, up[0], up[2], N, NP, grads)
-
-        # -------- FGRU
-        enc5 = acts["enc5"]
-        dy5 = w.get("dy:enc5", (enc5.C, enc5.L, NP))
-        self._bwd_fgru(w, N, NP, net.FGRU, up, acts["hout"], enc5, enc5, dy5, grads)
-        up = (dy5, enc5.t, enc5.bn)
+        up = self._bwd_bottleneck(w, acts, up, N, NP, grads)
 
         # -------- encoder 5..1: the data gradient accumulates onto the decoder's skip gradient stored in dy:enc{i-1}
         for i in range(5, 0, -1):
             prev = acts["enc%d" % (i - 1)]
-            dy_prev = w.get("dy:enc%d" % (i - 1), (prev.C, prev.L, NP))
+            dy_prev = self._fam(prev).alloc(w, "dy:enc%d" % (i - 1), prev.C, prev.L, NP)
             self._bwd_dsc(w, N, NP, net.encoder[i].DepthwiseSeparableConv1d, acts["enc%d.pw" % i], acts["enc%d" % i], up,
                           prev, prev, True, dy_prev, "dy:enc%d.pw" % i, grads)
             up = (dy_prev, prev.t, prev.bn)
