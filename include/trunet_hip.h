@@ -554,6 +554,53 @@ int trunet_reverb_mix(const float* clean, const float* noise, const float* rir, 
                       int early_taps, float peak, float* noisy, float* target, void* ws, size_t ws_bytes, int B, int L,
                       int Kmax, void* stream);
 
+/* ---- time-domain loss terms: segmental cosine similarity (cos_loss.py:4-56 repaired, R8) and SI-SDR ----
+ * x = audio (the estimate), y = clean, both (B, L) fp32.
+ * Cosine term: bounds[0 .. nseg] = 0, g[0], g[1], ... each clipped to L gives the nseg segments [bounds[i], bounds[i+1]):
+ *   cos_{b,i} = <x,y> / (c_x c_y),  c_x = max(|x|, cos_eps), c_y = max(|y|, cos_eps)  over the segment (the clamp of
+ *   torch.nn.CosineSimilarity: per norm); an empty segment has cos = 0 and no gradient;
+ *   L_cos = (1/nseg) sum_i mean_b (1 - cos_{b,i});
+ *   d L_cos / d x = w (a_y y + a_x x) on the segment, w = 1/(nseg B), a_y = -1/(c_x c_y),
+ *   a_x = <x,y> / (c_x^2 c_y |x|) when |x| > cos_eps, else 0; samples outside every segment get no gradient.
+ * SI-SDR term, per row over all L samples, both signals zero-mean (Sxy, Sxx, Syy the centred sums, d = si_sdr_eps):
+ *   alpha = Sxy/Syy, P = Sxy^2/Syy, N = Sxx - P, sisdr_b = 10 log10((P + d)/(N + d)), L_sisdr = -mean_b sisdr_b;
+ *   d sisdr_b / d x = c_y (y - mean y) + c_x (x - mean x), c_y = k (2 alpha/(P + d) + 2 alpha/(N + d)), c_x = -2k/(N + d),
+ *   k = 10/ln 10; a row with Syy == 0 contributes 0 and gets no gradient (the mean still divides by B).
+ * Work is split into items (segment, piece): piece k of segment i covers samples [s_i + k P, min(s_i + (k+1) P, e_i)),
+ * P = TRUNET_WAVE_LOSS_PIECE; segment nseg is the SI-SDR pseudo-segment [0, L).  The caller lists the items in the DEVICE
+ * table `items` (n_items, 2) = (segment, piece), segment by segment with pieces ascending, and seg_first (nseg + 2) holds
+ * the index of each segment's first item (seg_first[nseg + 1] = n_items).  A term without items is not computed: no
+ * SI-SDR items -> sisdr terms and coefficients are 0; nseg = 0 -> no cosine term.  A segment whose bounds are not
+ * increasing or leave [0, L], or whose item list is not exactly its pieces, is skipped: term 0, no gradient.
+ * trunet_wave_loss_fwd (2 launches): fp64 partial sums per item and row into ws, then one launch that writes
+ *   terms (B, nseg + 1): 1 - cos_{b,i} per segment, then sisdr_b;
+ *   coef (B, nseg + 1, 3) = (A, B_, C) with  d (weighted sum) / d x = A y + B_ x + C  on the segment (w, the lambdas and
+ *     the means included);
+ *   vals (5): [0] cos_lambda L_cos + si_sdr_lambda L_sisdr  [1] L_cos  [2] mean_b sisdr_b (dB)  [3] cos_lambda L_cos
+ *     [4] si_sdr_lambda L_sisdr;   loss_accum (may be NULL): loss_accum[0] += vals[0].
+ *   All of it fp64, rounded once on store.  No atomics: bit for bit repeatable; a row's terms and coefficients do not depend
+ *   on its batch-mates.  ws: trunet_wave_loss_workspace_bytes(B, L, nseg) bytes, 8-byte aligned (0 for extents out of range).
+ * trunet_wave_loss_grad (1 launch): g_audio[b][i] += g_loss[0] * sum over the segments containing i of (A y + B_ x + C).
+ * TRUNET_EINVAL before any launch: NULL buffers (loss_accum excepted), B outside [1, 65535], L outside [1, 2^30], nseg
+ * outside [0, TRUNET_WAVE_LOSS_MAX_SEG], n_items outside [1, 2 ceil(L/P) + nseg], a negative eps, a short or misaligned
+ * workspace, or a written buffer overlapping any other. */
+#define TRUNET_WAVE_LOSS_MAX_SEG 1024
+#define TRUNET_WAVE_LOSS_PIECE 2048
+typedef struct trunet_wave_loss_args {
+    const float* audio;          /* x (B, L) */
+    const float* clean;          /* y (B, L) */
+    const int32_t* bounds;       /* (nseg + 1) */
+    const int32_t* seg_first;    /* (nseg + 2) */
+    const int32_t* items;        /* (n_items, 2) */
+    int32_t B, L, nseg, n_items;
+    double cos_lambda, si_sdr_lambda, cos_eps, si_sdr_eps;
+} trunet_wave_loss_args;
+size_t trunet_wave_loss_workspace_bytes(int B, int L, int nseg);
+int trunet_wave_loss_fwd(const trunet_wave_loss_args* h_args, void* ws, size_t ws_bytes, float* vals, float* terms,
+                         float* coef, float* loss_accum, void* stream);
+int trunet_wave_loss_grad(const trunet_wave_loss_args* h_args, const float* coef, const float* g_loss, float* g_audio,
+                          void* stream);
+
 /* ======================================================================================================================
  * bf16 storage / bf16 MFMA family (BASELINE.json configs[2]; build extension: the reference has no reduced-precision path,
  * SURVEY 8d).  Activations and their gradients are stored as bf16 in the "octet" layout

@@ -122,6 +122,16 @@ class LossGatherArgs(C.Structure):
                 ("win_length", C.c_int32 * MAX_RES), ("nres", C.c_int32), ("_pad", C.c_int32)]
 
 
+MAX_WAVE_SEG, WAVE_PIECE = 1024, 2048       # trunet_hip.h: TRUNET_WAVE_LOSS_MAX_SEG, TRUNET_WAVE_LOSS_PIECE
+
+
+class WaveLossArgs(C.Structure):
+    """trunet_wave_loss_args"""
+    _fields_ = [(n, _fp) for n in ("audio", "clean", "bounds", "seg_first", "items")] + \
+               [(n, C.c_int32) for n in ("B", "L", "nseg", "n_items")] + \
+               [(n, C.c_double) for n in ("cos_lambda", "si_sdr_lambda", "cos_eps", "si_sdr_eps")]
+
+
 _lib = None
 
 
@@ -213,6 +223,9 @@ def _declare(L):
         "trunet_augment_mix": [p, p, p, p, p, i, i, p],
         "trunet_reverb_workspace_bytes": [i, i, i],
         "trunet_reverb_mix": [p, p, p, p, p, i, f, p, p, p, C.c_size_t, i, i, i, p],
+        "trunet_wave_loss_workspace_bytes": [i, i, i],
+        "trunet_wave_loss_fwd": [C.POINTER(WaveLossArgs), p, C.c_size_t, p, p, p, p, p],
+        "trunet_wave_loss_grad": [C.POINTER(WaveLossArgs), p, p, p, p],
         "trunet_stream_fwd_grid": [i],
         "trunet_stream_fwd_scratch_floats": [i],
         "trunet_stream_fwd_check": [C.POINTER(C.c_int32), i, i64, i],
@@ -251,6 +264,7 @@ def _declare(L):
     L.trunet_loss_scratch_bytes.restype = C.c_size_t
     L.trunet_stoi_workspace_bytes.restype = C.c_size_t
     L.trunet_reverb_workspace_bytes.restype = C.c_size_t
+    L.trunet_wave_loss_workspace_bytes.restype = C.c_size_t
     L._declared = sorted(sig)
 
 

@@ -78,11 +78,14 @@ _LOSS_SCRATCH = {}
 
 
 class _FusedLossFn(torch.autograd.Function):
-    """net output (B*T, 8, 257), clean (B, L) -> (loss, vals); vals = [loss, l1, stft_sc, stft_mag, ...] (no gradient)."""
+    """net output (B*T, 8, 257), clean (B, L) -> (loss, vals); vals = [loss, l1, stft_sc, stft_mag, ...] (no gradient).
+    With ``wave`` (the time-domain terms of cos_loss.py) -> (loss, vals, wave vals): the terms are added
+    to ``loss`` on the device by two more launches forward and one more backward; vals[0] stays the loss without them."""
 
     @staticmethod
-    def forward(ctx, net_out, clean, T, beta, stft_lambda, res, sc_lambda, mag_lambda):
+    def forward(ctx, net_out, clean, T, beta, stft_lambda, res, sc_lambda, mag_lambda, wave=None):
         # res: [(padded window, n, hop, win_length), ...] (empty: L1 only)
+        # wave: None or (g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps), g = () without the cosine term
         net_out = net_out.contiguous()
         B = net_out.shape[0] // T
         Ln = (T - 1) * HOP
@@ -122,14 +125,22 @@ class _FusedLossFn(torch.autograd.Function):
         loss = torch.empty((), device=dev, dtype=torch.float32)
         vals = torch.empty(5 + 2 * L.MAX_RES, device=dev, dtype=torch.float32)
         check(lib.trunet_loss_finalize(a, ptr(loss), ptr(vals), scratch.data_ptr(), st), "loss_finalize")
-        ctx.save_for_backward(net_out, clean, audio, tw, vals)
-        ctx.planes, ctx.T, ctx.beta = planes, T, beta
-        ctx.mark_non_differentiable(vals)
-        return loss, vals
+        ctx.planes, ctx.T, ctx.beta, ctx.wave = planes, T, beta, None
+        if wave is None:
+            ctx.save_for_backward(net_out, clean, audio, tw, vals)
+            ctx.mark_non_differentiable(vals)
+            return loss, vals
+        from . import cos_loss as cl
+        g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps = wave
+        ctx.wave = cl.wave_plan(Ln, g, si_sdr_lambda > 0, dev)
+        wvals, _, coef = cl.wave_forward(audio, clean, ctx.wave, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps, loss_accum=loss)
+        ctx.save_for_backward(net_out, clean, audio, tw, vals, coef)
+        ctx.mark_non_differentiable(vals, wvals)
+        return loss, vals, wvals
 
     @staticmethod
-    def backward(ctx, g_loss, _g_vals):
-        net_out, clean, audio, tw, vals = ctx.saved_tensors
+    def backward(ctx, g_loss, *_g_vals):
+        net_out, clean, audio, tw, vals = ctx.saved_tensors[:5]
         B, Ln = audio.shape
         lib, st = L.lib(), L.stream()
         g_loss = g_loss.reshape(1).float().contiguous()
@@ -139,10 +150,13 @@ class _FusedLossFn(torch.autograd.Function):
             a.fr_sc[i], a.fr_mag[i], a.n[i], a.hop[i], a.win_length[i] = ptr(fs), ptr(fm), n, hop, wl
         g = torch.empty_like(audio)
         check(lib.trunet_loss_grad_gather(a, ptr(audio), ptr(clean), ptr(vals), ptr(g_loss), ptr(g), B, Ln, st), "loss_grad_gather")
+        if ctx.wave is not None:
+            from . import cos_loss as cl
+            cl.wave_backward(audio, clean, ctx.wave, ctx.saved_tensors[5], g_loss, g)
         g_net = torch.empty_like(net_out)
         check(lib.trunet_mask_istft_bwd(ptr(g), ptr(net_out), ptr(g_net), ptr(tw), B, ctx.T, Ln, ctx.beta, st), "mask_istft_bwd")
         ctx.planes = None
-        return g_net, None, None, None, None, None, None, None
+        return g_net, None, None, None, None, None, None, None, None
 
 
 def _fused_loss_plan(mrstftloss, stft_lambda, dev):
@@ -165,9 +179,27 @@ def _fused_loss_plan(mrstftloss, stft_lambda, dev):
     return plan
 
 
-def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, **kwargs):
+def _wave_terms(cos_lambda, cos_config, si_sdr_lambda, si_sdr_eps):
+    """(g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps) for the time-domain terms that are switched on, else None"""
+    want_cos, want_si = bool(cos_lambda) and cos_lambda > 0, bool(si_sdr_lambda) and si_sdr_lambda > 0
+    if not (want_cos or want_si):
+        return None
+    from . import cos_loss as cl
+    g, cos_eps = (), 0.0
+    if want_cos:
+        m = cl.CosSimLoss(**(cos_config or {}))
+        g, cos_eps = tuple(m.g), m.eps
+    return g, float(cos_lambda) if want_cos else 0.0, cos_eps, float(si_sdr_lambda) if want_si else 0.0, float(si_sdr_eps)
+
+
+def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, cos_lambda=0, cos_config=None, si_sdr_lambda=0,
+            si_sdr_eps=1e-8, **kwargs):
     """util.py:186-251 (R7).  X = (clean_audio, noisy_audio), each (B, 1, L) (a leading batch-1 dim as the
-    reference's DataLoader gives, util.py:207, is squeezed).  Returns (loss, {"l1", "stft_sc", "stft_mag"})."""
+    reference's DataLoader gives, util.py:207, is squeezed).  Returns (loss, {"l1", "stft_sc", "stft_mag"}).
+
+    Opt-in time-domain terms (cos_loss.py): loss += cos_lambda * CosSimLoss(**cos_config)(audio, clean)
+    + si_sdr_lambda * SISDRLoss(si_sdr_eps)(audio, clean); cos_config = {"eps": ..., "g": ...} like stft_config.  The
+    dictionary then also carries "cos" and / or "si_sdr", the weighted terms.  Without them nothing changes."""
     clean_audio, noisy_audio = X
     if clean_audio.dim() == 4:
         clean_audio, noisy_audio = clean_audio.squeeze(0), noisy_audio.squeeze(0)
@@ -180,13 +212,21 @@ def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, **k
     # use_tgru (extension): the time-recurrent block needs to know where utterances begin
     out = net(feats, frames_per_seq=T) if getattr(net, "use_tgru", False) else net(feats)
     plan = _fused_loss_plan(mrstftloss, stft_lambda, out.device) if out.is_cuda else None
+    wave = _wave_terms(cos_lambda, cos_config, si_sdr_lambda, si_sdr_eps)
     if plan is not None:
-        loss, vals = _FusedLossFn.apply(out, clean.float(), T, 0.5, float(stft_lambda) if plan else 0.0, plan,
-                                        float(mrstftloss.sc_lambda) if plan else 0.0,
-                                        float(mrstftloss.mag_lambda) if plan else 0.0)
+        fused = (out, clean.float(), T, 0.5, float(stft_lambda) if plan else 0.0, plan,
+                 float(mrstftloss.sc_lambda) if plan else 0.0, float(mrstftloss.mag_lambda) if plan else 0.0)
+        if wave is None:
+            loss, vals = _FusedLossFn.apply(*fused)
+        else:
+            loss, vals, wvals = _FusedLossFn.apply(*fused, wave)
         output_dic = {"l1": vals[1]}
         if plan:
             output_dic["stft_sc"], output_dic["stft_mag"] = vals[2], vals[3]
+        if wave is not None and wave[1] > 0:
+            output_dic["cos"] = wvals[3]
+        if wave is not None and wave[3] > 0:
+            output_dic["si_sdr"] = wvals[4]
         return loss, output_dic
     den, l1 = denoise(out, clean, T)
     l1 = torch.abs(l1)
@@ -197,6 +237,17 @@ def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, **k
         loss = loss + (sc_loss + mag_loss) * stft_lambda
         output_dic["stft_sc"] = sc_loss.detach() * stft_lambda
         output_dic["stft_mag"] = mag_loss.detach() * stft_lambda
+    if wave is not None:
+        from . import cos_loss as cl
+        g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps = wave
+        if cos_lambda > 0:
+            cos = cl.CosSimLoss(eps=cos_eps, g=g)(den, clean)
+            loss = loss + cos * cos_lambda
+            output_dic["cos"] = cos.detach() * cos_lambda
+        if si_sdr_lambda > 0:
+            si = cl.SISDRLoss(eps=si_sdr_eps)(den, clean)
+            loss = loss + si * si_sdr_lambda
+            output_dic["si_sdr"] = si.detach() * si_sdr_lambda
     return loss, output_dic
 
 
