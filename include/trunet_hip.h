@@ -394,6 +394,42 @@ int trunet_stream_features_rows(float* ring, const float* chunks, float* pcen_M,
 int trunet_stream_mask_istft_rows(const float* net_out, float* ola, float* out, const int32_t* rows, int n_rows, int n_out,
                                   int slots, const float* tw512, float beta, void* stream);
 
+/* ---- stream pool, packets of any size (StreamPool.feed): every listed session brings a packet of n >= 0 samples and all the
+ * whole hops it completes are computed in the call.  Per slot the pool also keeps fifo (slots, 128): the 0..127 samples that
+ * wait for their hop to fill.  A frame is a 512-sample window of its session's LINE
+ *     ring[slot] (x[128 a0 - 512, 128 a0))  ++  fifo[slot][0, r0)  ++  samples[poff, poff + n)
+ * with a0 whole hops and r0 pending samples before the call; samples (n_samples) holds the packets back to back.
+ * rows: DEVICE array (n_rows, TRUNET_FEED_INTS) int32, record i = feature row i = net_out row i = frames row i:
+ *   [0] slot   [1] TRUNET_ROW_FIRST: frame 0, computed with the session's frame 1 (one transform, as the _rows entry points
+ *   pair them), whose features go to row [9]; TRUNET_ROW_STASHED: frame 1, nothing to transform   [2] t (informative)
+ *   [3] offset in the line of the window's first sample (FIRST: of x[0])   [4] r0   [5] n   [6] poff
+ *   [7] env: frames covering the hop this frame completes   [8] hop of `out` it goes to, -1: none   [9] FIRST: row of frame 1
+ * sess: DEVICE array (n_sess, TRUNET_FEED_INTS) int32, one record per listed session:
+ *   [0] slot   [1] flags (not read)   [2] seq0   [3] frames   [4] whole hops gained   [5] r0   [6] n   [7] poff
+ *   [8] r1 = r0 + n - 128 [4]: pending samples after the call   [9] position in the call (informative)
+ * seq: DEVICE array (n_rows) int32: seq[seq0 .. seq0 + frames) are the session's frame records in frame order.  Distinct
+ * sessions of a call name distinct slots.  A record whose slot, sample range, frame list or out hop lies outside the declared
+ * extents is skipped without touching state or data; every offset is an int32 and n_samples <= TRUNET_FEED_MAX_SAMPLES.
+ * trunet_stream_feed_features: per frame record, the features of ProcessAudio.forward -> feat (n_rows, C, 257); C = 4 leaves
+ *   the magnitude in channel 1.  Reads ring and fifo only.
+ * trunet_stream_feed_commit: per session, PCEN over its frames in frame order with the smoother carried in pcen_M[slot]
+ *   (FIRST: M = s x) replacing the magnitudes in feat; then ring[slot] <- line[128 [4], 128 [4] + 512) and fifo[slot] <- the
+ *   r1 samples after it.  n_rows may be 0 (sessions that only store samples).  Must follow trunet_stream_feed_features.
+ * trunet_stream_feed_mask_istft: net_out (n_rows, 8, 257) -> mask -> irFFT-512, unnormalised -> frames (n_rows, 512).
+ * trunet_stream_feed_ola: per session (the first n_sess records of sess: those with frames), its frames onto ola[slot]
+ *   (FIRST: the tail starts from zero) in frame order; after each frame out[hop [8]] (128) = the completed hop / env and
+ *   the tail moves on by a hop.  out (n_out, 128); n_out may be 0. */
+#define TRUNET_FEED_INTS 10
+#define TRUNET_FEED_MAX_SAMPLES 0x7fff0000
+int trunet_stream_feed_features(const float* ring, const float* fifo, const float* samples, float* feat, const int32_t* rows,
+                                int n_rows, int n_samples, int slots, const float* tw512, int C, void* stream);
+int trunet_stream_feed_commit(float* ring, float* fifo, const float* samples, float* pcen_M, float* feat, const int32_t* rows,
+                              const int32_t* sess, const int32_t* seq, int n_sess, int n_rows, int n_samples, int slots, int C,
+                              float eps, float s, float alpha, float delta, float r, void* stream);
+int trunet_stream_feed_mask_istft(const float* net_out, float* frames, int n_rows, const float* tw512, float beta, void* stream);
+int trunet_stream_feed_ola(const float* frames, float* ola, float* out, const int32_t* rows, const int32_t* sess,
+                           const int32_t* seq, int n_sess, int n_rows, int n_out, int slots, void* stream);
+
 /* ---- offline enhancement of B utterances of any lengths (enhance.py), packed back to back ----
  * audio holds sum L_b samples (L_b >= 257); sample_off[B+1] (prefix of L_b), frame_off[B+1] (prefix of T_b = 1 + L_b/128)
  * and pair_off[B+1] (prefix of ceil(T_b/2)) are int64 DEVICE arrays; total_* are their last entries.  Frames are paired

@@ -438,6 +438,22 @@ __global__ __launch_bounds__(256) void stream_mask_istft_kernel(const float* __r
     }
 }
 
+// The three per-element expressions every pool path shares (the _rows kernels below and the feed kernels after them): a
+// session's samples are the same bits whichever of the two ingests it, so the expressions exist once.
+//   pcen_smooth: the PCEN smoother, M[0] = s x[0], M[t] = (1 - s) M[t-1] + s x[t] (below)
+//   ola_add:     one frame sample (unnormalised inverse transform) onto the overlap-add tail
+//   env_div:     a completed sample over the number of frames that cover it
+// The smoother rounds both products and then adds them, the form the _rows kernel has always compiled to (its two products
+// share a v_pk_mul_f32).  Contraction is switched off for it: left to the compiler, `(1 - s) M + s x` stays that way in one
+// kernel and becomes one fused multiply-add in another -- a last-bit difference between the two ingests of the pool.
+__device__ __forceinline__ float pcen_smooth(bool first, float M, float mag, float s) {
+#pragma clang fp contract(off)
+    const float sx = s * mag;
+    return first ? sx : (1.f - s) * M + sx;
+}
+__device__ __forceinline__ float ola_add(float prev, float z) { return prev + z * (1.f / NF); }
+__device__ __forceinline__ float env_div(float v, float env) { return v / env; }
+
 // ---------------------------------------------------------------- stream pool: independent sessions behind a row table
 // The lockstep kernels above give every stream the same `first` / `env` and pack streams 2i and 2i+1 into one complex FFT, so a
 // stream's last bits depend on its neighbour.  The pool (streaming.StreamPool) runs sessions that start, pause and end on their
@@ -525,7 +541,7 @@ __global__ __launch_bounds__(256) void stream_features_rows_kernel(float* __rest
         float M = 0.f;
         if (C == 4) {
             float* Mp = pcen_M + (size_t)slot * BINS + k;
-            M = first ? s * mag : (1.f - s) * (*Mp) + s * mag;
+            M = pcen_smooth(first, first ? 0.f : *Mp, mag, s);
             if (!first) *Mp = M;
             o[BINS + k] = pcen_value(mag, M, eps, alpha, delta, r, dr);
         }
@@ -535,7 +551,7 @@ __global__ __launch_bounds__(256) void stream_features_rows_kernel(float* __rest
             sh[(size_t)(C - 2) * BINS + k] = sn;
             sh[(size_t)(C - 1) * BINS + k] = cs;
             if (C == 4) {
-                M = (1.f - s) * M + s * mag1;
+                M = pcen_smooth(false, M, mag1, s);
                 pcen_M[(size_t)slot * BINS + k] = M;
                 sh[BINS + k] = pcen_value(mag1, M, eps, alpha, delta, r, dr);
             }
@@ -570,17 +586,218 @@ __global__ __launch_bounds__(256) void stream_mask_istft_rows_kernel(const float
     float* acc = (float*)((z == sa) ? sb : sa);           // the other buffer: free after the transform
     float* ol = ola + (size_t)slot * NF;
     const bool first = (flags & TRUNET_ROW_FIRST) != 0;
-    for (int i = threadIdx.x; i < NF; i += 256) acc[i] = (first ? 0.f : ol[i]) + z[i].x * (1.f / NF);
+    for (int i = threadIdx.x; i < NF; i += 256) acc[i] = ola_add(first ? 0.f : ol[i], z[i].x);
     __syncthreads();
     const float fenv = (float)env;
     for (int i = threadIdx.x; i < NF; i += 256) {
         ol[i] = (i + HOPF < NF) ? acc[i + HOPF] : 0.f;
-        if (i < HOPF && orow >= 0) out[(size_t)orow * HOPF + i] = acc[i] / fenv;
+        if (i < HOPF && orow >= 0) out[(size_t)orow * HOPF + i] = env_div(acc[i], fenv);
     }
     if (finish && threadIdx.x < HOPF) {
-        out[(size_t)(orow + 1) * HOPF + threadIdx.x] = acc[HOPF + threadIdx.x] / 3.f;
-        out[(size_t)(orow + 2) * HOPF + threadIdx.x] = acc[2 * HOPF + threadIdx.x] / 2.f;
+        out[(size_t)(orow + 1) * HOPF + threadIdx.x] = env_div(acc[HOPF + threadIdx.x], 3.f);
+        out[(size_t)(orow + 2) * HOPF + threadIdx.x] = env_div(acc[2 * HOPF + threadIdx.x], 2.f);
     }
+}
+
+// ---------------------------------------------------------------- stream pool: packets of any size (StreamPool.feed)
+// A call brings every listed session a packet of any length; the session's new whole hops -- none, one or hundreds -- are all
+// computed in that call.  Per slot the pool keeps a FIFO of the 0..127 samples that wait for their hop to fill, and a frame of
+// the call is a 512-sample window of the session's LINE
+//     line = ring[slot] (512: x[128 a0 - 512, 128 a0))  ++  fifo[slot][0, r0)  ++  samples[poff, poff + n)
+// (a0 whole hops and r0 pending samples before the call, n the packet).  Four stages, each one launch whatever the sessions and
+// the burst lengths are:
+//   stream_feed_features   one workgroup per FRAME: the window from the line, the real-frame transform of
+//                          stream_features_rows_kernel (frames 0 and 1 of a session in one transform, as there), the spectral
+//                          features; with C = 4 the magnitude is left in the PCEN channel
+//   stream_feed_commit     one workgroup per SESSION: the PCEN smoother over the session's new frames in frame order (pcen_smooth
+//                          / pcen_value per bin, the magnitudes replaced in place), then the slot's ring and FIFO move on by the
+//                          call's whole hops.  A later launch than the frames: they all read the ring this one writes
+//   stream_feed_mask_istft one workgroup per frame: mask, Hermitian extension, inverse transform -> frames (n_rows, 512)
+//   stream_feed_ola        one workgroup per session: its frames onto the slot's overlap-add tail in ascending frame order
+//                          (ola_add), every completed hop over its envelope count (env_div), the tail shifted by a hop each time
+// Frame record = TRUNET_FEED_INTS int32; record i describes feature row i = net_out row i = frames row i:
+//   [0] slot  [1] flags (TRUNET_ROW_FIRST: frame 0, which also computes the session's frame 1 into row [9];
+//   TRUNET_ROW_STASHED: frame 1, nothing to transform)  [2] t (informative)  [3] offset of the window's first sample in the
+//   line (FIRST: of x[0])  [4] r0  [5] n  [6] poff  [7] env  [8] hop of `out` the completed hop goes to, -1: none  [9] FIRST: row
+//   of frame 1, else -1
+// Session record = TRUNET_FEED_INTS int32:
+//   [0] slot  [1] flags (unused by the kernels)  [2] seq0  [3] frames  [4] whole hops gained  [5] r0  [6] n  [7] poff  [8] r1
+//   [9] position in the call (informative); seq[seq0 .. seq0 + frames) are the session's frame records in frame order.
+// A record whose slot, sample range, frame list or out hop lies outside the declared extents is skipped by its whole workgroup
+// before any load from or store to the state and data buffers; line indices are clamped into the line.
+constexpr int FEED_INTS = TRUNET_FEED_INTS;
+
+struct FeedLine {
+    const float* rg;
+    const float* ff;
+    const float* pk;
+    int r0, n;
+};
+
+// slot and sample range of a record against the extents (uniform over the workgroup)
+__device__ __forceinline__ bool feed_line_ok(int slot, int r0, int n, int poff, int slots, int n_samples) {
+    return slot >= 0 && slot < slots && r0 >= 0 && r0 < HOPF && n >= 0 && poff >= 0 && n <= n_samples && poff <= n_samples - n;
+}
+
+__device__ __forceinline__ float feed_line_at(const FeedLine& l, int i) {
+    i = min(max(i, 0), NF + l.r0 + l.n - 1);
+    if (i < NF) return l.rg[i];
+    if (i < NF + l.r0) return l.ff[i - NF];
+    return l.pk[i - NF - l.r0];
+}
+
+// grid (n_rows); feat (n_rows, C, 257)
+__global__ __launch_bounds__(256) void stream_feed_features_kernel(const float* __restrict__ ring, const float* __restrict__ fifo,
+                                                                   const float* __restrict__ samples, float* __restrict__ feat,
+                                                                   const int* __restrict__ rows, int n_rows, int n_samples,
+                                                                   int slots, const cpx* __restrict__ tw, int C) {
+    __shared__ cpx sa[NF], sb[NF];
+    const int row = blockIdx.x;
+    const int* rec = rows + (size_t)row * FEED_INTS;
+    const int slot = rec[0], flags = rec[1], voff = rec[3], r0 = rec[4], n = rec[5], poff = rec[6], pair = rec[9];
+    if (flags & TRUNET_ROW_STASHED) return;              // frame 1: written by the session's FIRST row
+    const bool first = (flags & TRUNET_ROW_FIRST) != 0;
+    // all of this is uniform over the workgroup: a bad record leaves without a load or a store
+    if (!feed_line_ok(slot, r0, n, poff, slots, n_samples)) return;
+    if (voff < 0 || voff > r0 + n - (first ? 3 * HOPF - NF : 0)) return;       // FIRST needs x[0, 384), a frame its 512 samples
+    if (first && (pair < 0 || pair >= n_rows || pair == row)) return;
+    const FeedLine ln = {ring + (size_t)slot * NF, fifo + (size_t)slot * HOPF, samples + poff, r0, n};
+    for (int i = threadIdx.x; i < NF; i += 256) {
+        float v0, v1 = 0.f;
+        if (first) {
+            v0 = feed_line_at(ln, voff + reflect_idx(i - NF / 2, 3 * HOPF));
+            v1 = feed_line_at(ln, voff + reflect_idx(HOPF + i - NF / 2, 3 * HOPF));
+        } else {
+            v0 = feed_line_at(ln, voff + i);
+        }
+        sa[i] = make_float2(v0, v1);
+    }
+    const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    float* o = feat + ((size_t)row * C) * BINS;
+    float* o1 = feat + ((size_t)(first ? pair : row) * C) * BINS;
+    for (int k = threadIdx.x; k < BINS; k += 256) {
+        cpx X = Z[k], X1 = make_float2(0.f, 0.f);
+        if (first) split_pair(Z, k, NF, X, X1);
+        float nm, sn, cs;
+        const float mag = spectral_features(X.x, X.y, nm, sn, cs);
+        o[k] = nm;
+        o[(size_t)(C - 2) * BINS + k] = sn;
+        o[(size_t)(C - 1) * BINS + k] = cs;
+        if (C == 4) o[BINS + k] = mag;
+        if (first) {
+            const float mag1 = spectral_features(X1.x, X1.y, nm, sn, cs);
+            o1[k] = nm;
+            o1[(size_t)(C - 2) * BINS + k] = sn;
+            o1[(size_t)(C - 1) * BINS + k] = cs;
+            if (C == 4) o1[BINS + k] = mag1;
+        }
+    }
+}
+
+// the frame list of a session against n_rows: true if every entry names a frame record (uniform: ends with a barrier)
+__device__ __forceinline__ bool feed_seq_ok(const int* __restrict__ seq, int seq0, int nfr, int n_rows) {
+    if (seq0 < 0 || nfr < 0 || nfr > n_rows || seq0 > n_rows - nfr) return false;
+    int bad = 0;
+    for (int j = threadIdx.x; j < nfr; j += 256) {
+        const int r = seq[seq0 + j];
+        bad |= (r < 0 || r >= n_rows);
+    }
+    return __syncthreads_or(bad) == 0;
+}
+
+// grid (n_sess)
+__global__ __launch_bounds__(256) void stream_feed_commit_kernel(float* __restrict__ ring, float* __restrict__ fifo,
+                                                                 const float* __restrict__ samples, float* __restrict__ pcen_M,
+                                                                 float* __restrict__ feat, const int* __restrict__ rows,
+                                                                 const int* __restrict__ sess, const int* __restrict__ seq,
+                                                                 int n_rows, int n_samples, int slots, int C, float eps,
+                                                                 float s, float alpha, float delta, float r, float dr) {
+    const int* rec = sess + (size_t)blockIdx.x * FEED_INTS;
+    const int slot = rec[0], seq0 = rec[2], nfr = rec[3], adv = rec[4], r0 = rec[5], n = rec[6], poff = rec[7], r1 = rec[8];
+    if (!feed_line_ok(slot, r0, n, poff, slots, n_samples)) return;
+    if (r1 < 0 || r1 >= HOPF || adv < 0 || adv > (r0 + n) / HOPF || r0 + n - adv * HOPF != r1) return;
+    if (!feed_seq_ok(seq, seq0, nfr, n_rows)) return;
+    if (C == 4 && nfr > 0) {
+        for (int k = threadIdx.x; k < BINS; k += 256) {
+            float* Mp = pcen_M + (size_t)slot * BINS + k;
+            float M = *Mp;
+            for (int j = 0; j < nfr; ++j) {
+                const int row = seq[seq0 + j];
+                const bool first = (rows[(size_t)row * FEED_INTS + 1] & TRUNET_ROW_FIRST) != 0;
+                float* o = feat + ((size_t)row * C + 1) * BINS + k;
+                const float mag = *o;
+                M = pcen_smooth(first, M, mag, s);
+                *o = pcen_value(mag, M, eps, alpha, delta, r, dr);
+            }
+            *Mp = M;
+        }
+    }
+    // ring <- line[128 adv, 128 adv + 512), fifo <- the r1 samples after it: everything is read before anything is written
+    const FeedLine ln = {ring + (size_t)slot * NF, fifo + (size_t)slot * HOPF, samples + poff, r0, n};
+    const int t = threadIdx.x, base = adv * HOPF;
+    const float v0 = feed_line_at(ln, base + t), v1 = feed_line_at(ln, base + 256 + t);
+    const float v2 = (t < r1) ? feed_line_at(ln, base + NF + t) : 0.f;
+    __syncthreads();
+    if (adv > 0) {
+        ring[(size_t)slot * NF + t] = v0;
+        ring[(size_t)slot * NF + 256 + t] = v1;
+    }
+    if (t < r1) fifo[(size_t)slot * HOPF + t] = v2;
+}
+
+// grid (n_rows); net_out (n_rows, 8, 257) -> frames (n_rows, 512): the real part of the unnormalised inverse transform
+__global__ __launch_bounds__(256) void stream_feed_mask_istft_kernel(const float* __restrict__ net_out,
+                                                                     float* __restrict__ frames, const cpx* __restrict__ tw,
+                                                                     float beta) {
+    __shared__ cpx sa[NF], sb[NF];
+    const int row = blockIdx.x;
+    for (int k = threadIdx.x; k < BINS; k += 256) {
+        const MaskVals v = mask_vals(net_out + (size_t)row * 8 * BINS + k, BINS, beta);
+        const float M = v.S * v.A;
+        cpx X = make_float2(M * v.cm, M * v.sm);
+        if (k == 0 || k == NF / 2) X.y = 0.f;            // c2r ignores the imaginary part of DC / Nyquist
+        sa[k] = X;
+        if (k > 0 && k < NF / 2) sa[NF - k] = make_float2(X.x, -X.y);
+    }
+    const cpx* z = fft_lds_t<9, true>(sa, sb, tw);
+    for (int i = threadIdx.x; i < NF; i += 256) frames[(size_t)row * NF + i] = z[i].x;
+}
+
+// grid (sessions that have frames); out (n_out, 128)
+__global__ __launch_bounds__(256) void stream_feed_ola_kernel(const float* __restrict__ frames, float* __restrict__ ola,
+                                                              float* __restrict__ out, const int* __restrict__ rows,
+                                                              const int* __restrict__ sess, const int* __restrict__ seq,
+                                                              int n_rows, int n_out, int slots) {
+    __shared__ float acc[NF];
+    const int* rec = sess + (size_t)blockIdx.x * FEED_INTS;
+    const int slot = rec[0], seq0 = rec[2], nfr = rec[3];
+    if (slot < 0 || slot >= slots || nfr < 1) return;
+    if (!feed_seq_ok(seq, seq0, nfr, n_rows)) return;
+    int bad = 0;
+    for (int j = threadIdx.x; j < nfr; j += 256) {
+        const int* fr = rows + (size_t)seq[seq0 + j] * FEED_INTS;
+        bad |= (fr[7] < 1 || fr[8] < -1 || fr[8] >= n_out);
+    }
+    if (__syncthreads_or(bad)) return;
+    const int t = threadIdx.x;
+    float* ol = ola + (size_t)slot * NF;
+    float t0 = ol[t], t1 = ol[256 + t];
+    for (int j = 0; j < nfr; ++j) {
+        const int row = seq[seq0 + j];
+        const int* fr = rows + (size_t)row * FEED_INTS;
+        const bool first = (fr[1] & TRUNET_ROW_FIRST) != 0;
+        const int orow = fr[8];
+        const float fenv = (float)fr[7];
+        acc[t] = ola_add(first ? 0.f : t0, frames[(size_t)row * NF + t]);
+        acc[256 + t] = ola_add(first ? 0.f : t1, frames[(size_t)row * NF + 256 + t]);
+        __syncthreads();
+        if (t < HOPF && orow >= 0) out[(size_t)orow * HOPF + t] = env_div(acc[t], fenv);
+        t0 = acc[t + HOPF];
+        t1 = (t + HOPF < 256) ? acc[256 + t + HOPF] : 0.f;
+        __syncthreads();
+    }
+    ol[t] = t0;
+    ol[256 + t] = t1;
 }
 
 // One windowed frame pair z = w x + j w y into LDS, and the n/2 twiddles next to it.  NI = n / 256 is a COMPILE-TIME
@@ -1322,6 +1539,46 @@ extern "C" int trunet_stream_mask_istft_rows(const float* net_out, float* ola, f
     if (!net_out || !ola || !out || !rows || !tw512 || n_rows <= 0 || n_out <= 0 || slots <= 0) return TRUNET_EINVAL;
     hipLaunchKernelGGL(stream_mask_istft_rows_kernel, dim3(n_rows), dim3(256), 0, ST, net_out, ola, out, rows, n_out, slots,
                        (const cpx*)tw512, beta);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stream_feed_features(const float* ring, const float* fifo, const float* samples, float* feat,
+                                           const int32_t* rows, int n_rows, int n_samples, int slots, const float* tw512, int C,
+                                           void* stream) {
+    if (!ring || !fifo || !feat || !rows || !tw512 || n_rows <= 0 || n_samples < 0 || n_samples > TRUNET_FEED_MAX_SAMPLES ||
+        (n_samples > 0 && !samples) || slots <= 0 || (C != 3 && C != 4))
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stream_feed_features_kernel, dim3(n_rows), dim3(256), 0, ST, ring, fifo, samples, feat, rows, n_rows,
+                       n_samples, slots, (const cpx*)tw512, C);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stream_feed_commit(float* ring, float* fifo, const float* samples, float* pcen_M, float* feat,
+                                         const int32_t* rows, const int32_t* sess, const int32_t* seq, int n_sess, int n_rows,
+                                         int n_samples, int slots, int C, float eps, float s, float alpha, float delta, float r,
+                                         void* stream) {
+    if (!ring || !fifo || !sess || n_sess <= 0 || n_rows < 0 || n_samples < 0 || n_samples > TRUNET_FEED_MAX_SAMPLES ||
+        (n_samples > 0 && !samples) || slots <= 0 || (n_rows > 0 && (!feat || !rows || !seq)) || (C != 3 && C != 4) || (C == 4 && !pcen_M))
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stream_feed_commit_kernel, dim3(n_sess), dim3(256), 0, ST, ring, fifo, samples, pcen_M, feat, rows, sess,
+                       seq, n_rows, n_samples, slots, C, eps, s, alpha, delta, r, powf(delta, r));
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stream_feed_mask_istft(const float* net_out, float* frames, int n_rows, const float* tw512, float beta,
+                                             void* stream) {
+    if (!net_out || !frames || !tw512 || n_rows <= 0) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stream_feed_mask_istft_kernel, dim3(n_rows), dim3(256), 0, ST, net_out, frames, (const cpx*)tw512, beta);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stream_feed_ola(const float* frames, float* ola, float* out, const int32_t* rows, const int32_t* sess,
+                                      const int32_t* seq, int n_sess, int n_rows, int n_out, int slots, void* stream) {
+    if (!frames || !ola || !rows || !sess || !seq || n_sess <= 0 || n_rows <= 0 || n_sess > n_rows || n_out < 0 ||
+        (n_out > 0 && !out) || slots <= 0)
+        return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stream_feed_ola_kernel, dim3(n_sess), dim3(256), 0, ST, frames, ola, out, rows, sess, seq, n_rows, n_out,
+                       slots);
     return trunet_launch_status();
 }
 

@@ -241,6 +241,98 @@ def plan_close(hops, tails, slots=None):
     return ClosePlan(tables, [len(t) for t in tables], (L - HOP * np.maximum(a - 3, 0)).tolist())
 
 
+# ---- packets of any size (StreamPool.feed).  A call's plan is three int32 tables that go to the device in ONE copy (trunet_hip.h:
+# TRUNET_FEED_INTS and the text above it):
+#   rows   one record per STFT frame of the call; record i is feature row i, network row i and frames row i.  Laid out DEPTH-MAJOR:
+#          first the first new frame of every session that has one, then the second, ...; sessions are ordered by their number of
+#          new frames, most first, so depth d is the contiguous slice depths[d] = (lo, hi) and its sessions are the first hi - lo
+#          of `sess` -- what the time-recurrent block needs, one network launch per depth.
+#   sess   one record per listed session, in that order (``order[j]``: its position in the call)
+#   seq    per session, its frame records in frame order
+FEED_INTS = 10                        # trunet_hip.h: TRUNET_FEED_INTS
+FEED_MAX_SAMPLES = 0x7fff0000         # trunet_hip.h: TRUNET_FEED_MAX_SAMPLES
+INT32_MAX = 2 ** 31 - 1
+FeedRow = namedtuple("FeedRow", "slot flags frame off r0 n poff env out pair")
+FeedSess = namedtuple("FeedSess", "slot flags seq0 frames adv r0 n poff r1 pos")
+# lengths: samples each listed session gets back; hops, pending: per listed session after the call; out_off: the hop of the
+# call's output its samples start at; n_active: sessions that have frames (the first n_active records of sess)
+FeedPlan = namedtuple("FeedPlan", "rows sess seq depths lengths hops pending out_off n_active n_out n_samples")
+
+
+def feed_rows_of(table):
+    """the frame records of a feed plan as a list of FeedRow"""
+    return [FeedRow(*(int(v) for v in r)) for r in table]
+
+
+def plan_feed(hops, pending, lengths, listed):
+    """What one ``feed`` owes.  hops[slot], pending[slot]: whole hops received and samples waiting (0..127) BEFORE the call;
+    listed: the slots that bring a packet; lengths[i]: samples in the packet of listed[i] (0 allowed).
+
+    With a1 = (128 a0 + r0 + n) // 128 and r1 = (r0 + n) % 128 a session computes frames 0 and 1 when a1 >= 3 > a0, then
+    every frame t with max(a0 - 1, 2) <= t <= a1 - 2, and gets back 128 (max(a1 - 3, 0) - max(a0 - 3, 0)) samples: exactly
+    the frames, flags, envelope counts and output order of a1 - a0 calls of ``plan_step``.  ValueError, with nothing
+    changed, for a slot listed twice, lengths that do not match the ids, a negative length and totals beyond int32."""
+    listed = np.asarray(listed, dtype=np.int64).reshape(-1)
+    n = np.asarray(lengths)
+    if n.ndim != 1 or n.shape[0] != listed.shape[0]:
+        raise ValueError("%d packet lengths for %d sessions" % (n.size if n.ndim == 1 else -1, listed.shape[0]))
+    if n.size and n.dtype.kind not in "iu":
+        raise ValueError("packet lengths are integers, got %s" % n.dtype)
+    n = n.astype(np.int64)
+    if (n < 0).any():
+        raise ValueError("a packet cannot have a negative length: %s" % n[n < 0].tolist())
+    if np.unique(listed).shape[0] != listed.shape[0]:
+        raise ValueError("a slot is listed twice: %s" % (listed.tolist(),))
+    ns = listed.shape[0]
+    a0 = np.asarray(hops, dtype=np.int64)[listed]
+    r0 = np.asarray(pending, dtype=np.int64)[listed]
+    n_samples = int(n.sum())                                    # python int: no wrap-around
+    if n_samples > FEED_MAX_SAMPLES or (ns and int(n.max()) > FEED_MAX_SAMPLES):
+        raise ValueError("%d samples in one call: offsets into the packed buffers are int32 (at most %d)"
+                         % (n_samples, FEED_MAX_SAMPLES))
+    adv = (r0 + n) // HOP
+    a1, r1 = a0 + adv, (r0 + n) % HOP
+    start = (a0 < 3) & (a1 >= 3)
+    lo = np.maximum(a0 - 1, 2)                                  # first steady frame
+    emit = np.maximum(a1 - 2 - lo + 1, 0)                       # frames t >= 2: one output hop each
+    nfr = emit + 2 * start
+    n_rows, n_out = int(nfr.sum()), int(emit.sum())
+    if n_rows * 8 * BINS > INT32_MAX:
+        raise ValueError("%d frames in one call: offsets into the packed buffers are int32" % n_rows)
+    poff, out_off = np.cumsum(n) - n, np.cumsum(emit) - emit
+    order = np.argsort(-nfr, kind="stable")                     # most frames first
+    fs = nfr[order]
+    depth = int(fs[0]) if ns else 0
+    cnt = ns - np.searchsorted(fs[::-1], np.arange(depth), side="right")       # sessions with more than d frames
+    doff = np.cumsum(cnt) - cnt
+    d = np.repeat(np.arange(depth), cnt)                        # per frame record: its depth ...
+    j = np.arange(n_rows) - np.repeat(doff, cnt)                # ... and its session (index into order)
+    sidx = order[j]
+    st = start[sidx]
+    t = np.where(st, d, lo[sidx] + d)
+    first, second = st & (d == 0), st & (d == 1)
+    rows = np.zeros((n_rows, FEED_INTS), dtype=np.int32)
+    if n_rows:
+        rows[:, 0] = listed[sidx]
+        rows[:, 1] = np.where(first, ROW_FIRST, 0) | np.where(second, ROW_STASHED, 0)
+        rows[:, 2] = np.minimum(t, INT32_MAX)
+        rows[:, 3] = np.where(first, N_FFT - HOP * a0[sidx], HOP * (t - a0[sidx]) + N_FFT // 2)
+        rows[:, 4], rows[:, 5], rows[:, 6] = r0[sidx], n[sidx], poff[sidx]
+        rows[:, 7] = np.where(t < 2, t + 1, hop_env(t - 2))
+        rows[:, 8] = np.where(t >= 2, out_off[sidx] + t - lo[sidx], -1)
+        rows[:, 9] = np.where(first, (doff[1] if depth > 1 else 0) + j, -1)
+    seq0 = np.cumsum(fs) - fs
+    seq = np.zeros(n_rows, dtype=np.int32)
+    seq[seq0[j] + d] = np.arange(n_rows)
+    sess = np.zeros((ns, FEED_INTS), dtype=np.int32)
+    for c, v in enumerate((listed[order], np.where(start[order], ROW_FIRST, 0), seq0, fs, adv[order], r0[order], n[order],
+                           poff[order], r1[order], order)):
+        sess[:, c] = v
+    depths = [(int(o), int(o + c)) for o, c in zip(doff, cnt)]
+    return FeedPlan(rows, sess, seq, depths, (HOP * emit).tolist(), a1, r1, out_off, int(cnt[0]) if depth else 0, n_out,
+                    n_samples)
+
+
 class SlotAllocator:
     """Free list of a fixed number of state slots: the lowest free id first, an id is never out twice."""
 
@@ -282,6 +374,9 @@ class StreamPool:
         rest = pool.close(ids, tails)           # list of 1-D tensors; tails[i]: the 0..127 last samples of session i, or None
         pool.abort(ids)                         # drop sessions without output
         pool.free, pool.capacity, pool.hops(id)
+        outs = pool.feed(packets, ids)          # packets of ANY size: list of n 1-D fp32 cuda tensors, or (packed, lengths)
+        pool.pending(id)                        # samples of a fed session that wait for their hop to fill: 0..127
+        rest = pool.close(ids)                  # a fed session's tail is what is pending: no tails needed
 
     A session that received ``a`` hops and a tail of ``r`` samples is the utterance x of L = 128 a + r samples, and the rows
     of ``out`` where ``valid`` is set followed by ``rest`` are ``net.enhance([x])[0]``: L samples.  Latency as in
@@ -302,7 +397,22 @@ class StreamPool:
     ``synchronize``; ``valid`` comes from the host's hop counts.  Slot ids are host data (a list or a CPU integer tensor).
     Every misuse raises before anything reaches the device and leaves all sessions as they were.  The row count changes from
     step to step, so a pool step is not captured as a hipGraph; ``AudioStream`` remains the graph-replayable lockstep path.
-    The weights are those of the folded (or int8) artefact taken at construction."""
+    The weights are those of the folded (or int8) artefact taken at construction.
+
+    ``feed`` is the ingress for transports that do not deliver 128-sample units (RTP's 160 or 320 samples, a jitter buffer
+    that drains several packets, a second of audio after a stall).  Per slot the pool keeps a FIFO of the 0..127 samples
+    that have not filled a hop; a session that had a0 hops and r0 pending samples and gets n more has a1 = (128 a0 + r0 + n)
+    // 128 hops and r1 = (r0 + n) % 128 pending, computes frames 0 and 1 when a1 >= 3 > a0 and every frame t with
+    max(a0 - 1, 2) <= t <= a1 - 2, and gets back 128 (max(a1 - 3, 0) - max(a0 - 3, 0)) samples.  However the utterance is
+    cut -- empty packets, single samples, everything at once -- the samples are bit for bit those of ``step`` /
+    ``close(tails)``: the kernels share the per-element expressions and keep their order.  All new frames
+    of all listed sessions go through ONE pass (``plan_feed``): trunet_stream_feed_features (a workgroup per frame),
+    trunet_stream_feed_commit (per session: PCEN in frame order, ring and FIFO move on), the network on all rows at once
+    (with ``tgru``: once per burst depth, the rows laid out depth-major so that each launch reads a contiguous slice; at most
+    ``net.fold_max_frames`` rows per launch either way), trunet_stream_feed_mask_istft (per frame), trunet_stream_feed_ola
+    (per session: overlap-add in frame order).  No synchronisation with the device, one copy of the plan per call.  ``step``
+    and ``feed`` may alternate on a session while nothing is pending; ``step``, or ``close`` with a tail, on a session with
+    pending samples is a ValueError that changes nothing."""
 
     def __init__(self, net, slots, tgru=None, beta=0.5, int8=False):
         if net.training:
@@ -329,8 +439,10 @@ class StreamPool:
         self.pcen_M = z(S, BINS) if self.C == 4 else None
         self.stash = z(S, self.C, BINS)                          # frame 1's features between a session's first two passes
         self.h = self.run.new_state(S, dev) if self.tgru else None           # TGRU state (slots, 128, 16)
+        self.fifo = z(S, HOP)                                    # feed(): the 0..127 samples that wait for their hop to fill
         self.tw = L.twiddles(N_FFT, dev)
         self._hops = np.zeros(S, dtype=np.int64)
+        self._pend = np.zeros(S, dtype=np.int64)                 # samples in the FIFO, per slot
 
     # ---- host-side bookkeeping
     @property
@@ -345,12 +457,17 @@ class StreamPool:
         """whole hops session ``slot`` has received"""
         return int(self._hops[self._ids([slot])[0]])
 
+    def pending(self, slot):
+        """samples of session ``slot`` that wait for their hop to fill (``feed``): 0..127, a host value"""
+        return int(self._pend[self._ids([slot])[0]])
+
     def open(self, n=1):
         """n new sessions -> their slot ids; raises when fewer than n slots are free.  Host work only: the first frame of a
         session overwrites the slot's state."""
         ids = self._alloc.open(n)
         for i in ids:
             self._hops[i] = 0
+            self._pend[i] = 0
         return ids
 
     def abort(self, ids):
@@ -421,6 +538,7 @@ class StreamPool:
                                    % (self.dev, chunks.device))
         if tuple(chunks.shape) != (len(ids), HOP):
             raise ValueError("expected (%d, %d) samples, got %s" % (len(ids), HOP, tuple(chunks.shape)))
+        self._no_pending(ids, "step() takes whole hops")
         out = torch.zeros((len(ids), HOP), device=self.dev, dtype=torch.float32)
         if not len(ids):
             return out, torch.zeros(0, dtype=torch.bool)
@@ -430,20 +548,136 @@ class StreamPool:
         self._hops[ids] = plan.hops
         return out, torch.from_numpy(plan.valid)
 
+    # ---- packets of any size
+    def _no_pending(self, ids, what):
+        bad = self._pend[ids] != 0
+        if bad.any():
+            raise ValueError("%s: session %s has pending samples from feed() (%s); go on with feed(), or close()"
+                             % (what, ids[bad].tolist(), self._pend[ids][bad].tolist()))
+
+    def _packets(self, packets, n):
+        """-> (list of 1-D device tensors to concatenate, lengths); host checks only"""
+        if isinstance(packets, tuple) and len(packets) == 2 and torch.is_tensor(packets[0]) and not (
+                torch.is_tensor(packets[1]) and packets[1].is_cuda):
+            flat, lens = packets
+            if torch.is_tensor(lens):
+                lens = lens.numpy()
+            lens = np.asarray(lens)
+            if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
+                raise ValueError("packet lengths: a 1-D sequence of host integers, got %s %s" % (lens.dtype, lens.shape))
+            parts, total = [flat], int(lens.astype(np.int64).sum()) if lens.size else 0
+            if flat.dim() != 1 or flat.shape[0] != total:
+                raise ValueError("the packed samples: a 1-D tensor of sum(lengths) = %d samples, got %s"
+                                 % (total, tuple(flat.shape)))
+        else:
+            if torch.is_tensor(packets) or not isinstance(packets, (list, tuple)):
+                raise ValueError("packets: a list of 1-D tensors, or (packed 1-D tensor, lengths), got %s"
+                                 % type(packets).__name__)
+            parts = list(packets)
+            for i, t in enumerate(parts):
+                if not torch.is_tensor(t) or t.dim() != 1:
+                    raise ValueError("packet %d: expected a 1-D tensor, got %s"
+                                     % (i, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+            lens = np.array([t.shape[0] for t in parts], dtype=np.int64)
+        if lens.shape[0] != n:
+            raise ValueError("%d packets for %d sessions" % (lens.shape[0], n))
+        for i, t in enumerate(parts):
+            if not t.is_cuda or t.device != self.dev:
+                raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: the pool sits on %s, packet %d is a %s tensor"
+                                       % (self.dev, i, t.device))
+            if not t.dtype.is_floating_point:
+                raise ValueError("packet %d: samples are floating point, got %s" % (i, t.dtype))
+        return parts, lens
+
+    def _net_rows(self, feat, rows, lo, hi, first):
+        """the network on feature rows [lo, hi), at most net.fold_max_frames per launch; with the time-recurrent block the
+        rows are one frame each of distinct sessions and their slots' states step with them"""
+        step = max(int(self.net.fold_max_frames), 1)
+        ys = []
+        for b in range(lo, hi, step):
+            e = min(b + step, hi)
+            if self.tgru:
+                idx = rows[b:e, 0].long()
+                h = self.h.index_select(0, idx)
+                if first:                                       # h0 = 0 like nn.GRU, whatever the slot's last session left
+                    h.masked_fill_(((rows[b:e, 1] & ROW_FIRST) != 0)[:, None, None], 0.0)
+                ys.append(self.run.stream_step(feat[b:e], h))
+                self.h.index_copy_(0, idx, h)
+            else:
+                ys.append(self.run(feat[b:e]))
+        return ys
+
+    @torch.no_grad()
+    def feed(self, packets, ids):
+        """A packet of ANY length (0 allowed) for each listed session: packets is a list of n 1-D fp32 tensors on the pool's
+        device, or a pair (packed 1-D tensor, lengths as host integers); ids n distinct open slots.  Returns n 1-D tensors
+        (views of one buffer): the denoised samples of each session that became final with this call, possibly none.
+
+        However an utterance is cut into packets, what ``feed`` returned for it, concatenated and followed by ``close(ids)``,
+        is bit for bit the ``step`` / ``close(tails)`` result.  Samples that do not fill a hop wait in the slot's FIFO
+        (``pending``); ``step`` and ``feed`` may alternate while nothing is pending.  Never synchronises with the device;
+        the plan of the call goes up in one copy."""
+        ids = self._ids(ids)
+        parts, lens = self._packets(packets, len(ids))
+        plan = plan_feed(self._hops, self._pend, lens, ids)
+        if not len(ids):
+            return []
+        lib, st, p, dev = L.lib(), L.stream(), PCEN, self.dev
+        n_rows, n_sess, S = len(plan.rows), len(plan.sess), self.capacity
+        samples = None
+        if plan.n_samples:
+            parts = [t for t in parts if t.shape[0]]
+            samples = (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous().float()
+        tab = torch.from_numpy(np.concatenate([plan.rows.reshape(-1), plan.sess.reshape(-1), plan.seq])).to(dev)   # ONE copy
+        rows = tab[:n_rows * FEED_INTS].view(n_rows, FEED_INTS)
+        sess = tab[n_rows * FEED_INTS:(n_rows + n_sess) * FEED_INTS]
+        seq = tab[(n_rows + n_sess) * FEED_INTS:]
+        prow, pseq = (rows.data_ptr(), seq.data_ptr()) if n_rows else (None, None)
+        feat = None
+        if n_rows:
+            feat = torch.empty((n_rows, self.C, BINS), device=dev, dtype=torch.float32)
+            check(lib.trunet_stream_feed_features(ptr(self.ring), ptr(self.fifo), ptr(samples), ptr(feat), prow, n_rows,
+                                                  plan.n_samples, S, ptr(self.tw), self.C, st), "stream_feed_features")
+        check(lib.trunet_stream_feed_commit(ptr(self.ring), ptr(self.fifo), ptr(samples), ptr(self.pcen_M), ptr(feat), prow,
+                                            sess.data_ptr(), pseq, n_sess, n_rows, plan.n_samples, S, self.C, p["eps"], p["s"],
+                                            p["alpha"], p["delta"], p["r"], st), "stream_feed_commit")
+        out = torch.empty(plan.n_out * HOP, device=dev, dtype=torch.float32)
+        if n_rows:
+            if self.tgru:                                       # one launch per burst depth: the d-th new frame of every session
+                ys = [y for d, (lo, hi) in enumerate(plan.depths) for y in self._net_rows(feat, rows, lo, hi, d == 0)]
+            else:                                               # frames are independent: all of them at once
+                ys = self._net_rows(feat, rows, 0, n_rows, False)
+            y = ys[0] if len(ys) == 1 else torch.cat(ys)
+            frames = torch.empty((n_rows, N_FFT), device=dev, dtype=torch.float32)
+            check(lib.trunet_stream_feed_mask_istft(ptr(y), ptr(frames), n_rows, ptr(self.tw), self.beta, st),
+                  "stream_feed_mask_istft")
+            check(lib.trunet_stream_feed_ola(ptr(frames), ptr(self.ola), ptr(out) if plan.n_out else None, prow,
+                                             sess.data_ptr(), pseq, plan.n_active, n_rows, plan.n_out, S, st),
+                  "stream_feed_ola")
+        self._hops[ids] = plan.hops
+        self._pend[ids] = plan.pending
+        return [out[HOP * int(o):HOP * int(o) + m] for o, m in zip(plan.out_off, plan.lengths)]
+
     @torch.no_grad()
     def close(self, ids, tails=None):
         """End sessions: tails[i] (None, or a 1-D fp32 tensor of 0..127 samples on the pool's device) are the samples after
-        session i's last whole hop.  Returns, per session, the L - 128 max(a - 3, 0) samples not yet delivered, and frees the
-        slots.  ValueError for a session of fewer than 257 samples; it stays open, like every other session of the call."""
+        session i's last whole hop.  A session with pending samples from ``feed`` has them as its tail already: ``close(ids)``;
+        giving it a tail as well is a ValueError.  Returns, per session, the L - 128 max(a - 3, 0) samples not yet delivered,
+        and frees the slots.  ValueError for a session of fewer than 257 samples; it stays open, like every other session of
+        the call."""
         ids = self._ids(ids)
         tails = [None] * len(ids) if tails is None else list(tails)
         if len(tails) != len(ids):
             raise ValueError("%d tails for %d sessions" % (len(tails), len(ids)))
         rs = []
+        pend = self._pend[ids]
         for i, t in enumerate(tails):
             if t is None:
-                rs.append(0)
+                rs.append(int(pend[i]))                          # a fed session: its tail is what waits in the FIFO
                 continue
+            if pend[i]:
+                raise ValueError("tail %d: session %d has %d pending samples from feed(), they are its tail"
+                                 % (i, ids[i], pend[i]))
             if not torch.is_tensor(t) or t.dim() != 1:
                 raise ValueError("tail %d: expected a 1-D tensor or None" % i)
             if t.shape[0] >= HOP:
@@ -458,11 +692,14 @@ class StreamPool:
             return []
         n = len(ids)
         tl, n_tl = None, 0
-        if any(rs):
+        if pend.any():                                          # rows of the FIFO; what lies past a row's r samples is not read
+            tl, n_tl = self.fifo.index_select(0, torch.from_numpy(ids).to(self.dev)), n
+        elif any(rs):
             tl, n_tl = torch.zeros((n, HOP), device=self.dev, dtype=torch.float32), n
-            where = np.concatenate([HOP * i + np.arange(r) for i, r in enumerate(rs) if r])
-            tl.view(-1).index_copy_(0, torch.from_numpy(where).to(self.dev),
-                                    torch.cat([t.float() for t, r in zip(tails, rs) if r]))
+        given = [i for i, (t, r) in enumerate(zip(tails, rs)) if t is not None and r]
+        if given:
+            where = np.concatenate([HOP * i + np.arange(rs[i]) for i in given])
+            tl.view(-1).index_copy_(0, torch.from_numpy(where).to(self.dev), torch.cat([tails[i].float() for i in given]))
         out = torch.zeros((n, CLOSE_OUT_ROWS * HOP), device=self.dev, dtype=torch.float32)
         self._run_passes(plan, tl, n_tl, out, n * CLOSE_OUT_ROWS)
         self._alloc.release(ids)
