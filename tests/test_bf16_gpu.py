@@ -430,7 +430,8 @@ def test_bf16_layout_round_trip():
 
 def test_bf16_gru_kernels_match_the_fp32_recurrence_on_the_same_operands():
     """trunet_bf16_gru_fwd / _bwd (round 3: the bidirectional recurrence with octet tensors on both sides) against the fp32
-    kernels trunet_gru_fwd / _bwd (pinned by block_gru_bi.npz and the fp64 oracle) on the SAME bf16-representable operands:
+    kernels trunet_gru_fwd / _bwd (pinned by block_gru_bi.npz and the fp64 oracle, and on their own against the fp64 recurrence by
+    tests/test_gru_gpu.py) on the SAME bf16-representable operands:
     the arithmetic inside is the same fp32 arithmetic, so every stored value may differ by the final bf16 rounding only
     (one ulp = 2^-8 relative where the two fp32 values straddle a rounding boundary).  Ragged workgroup count (NP = 384)."""
     from tinyrecurrentunet_amd import _lib as L
@@ -487,7 +488,7 @@ def test_bf16_gru_backward_vs_the_exact_fp32_recurrence():
     """bgru_bwd_kernel takes h_{t-1} from the bf16-rounded recurrence output and r, z, n, gh from bf16 gate planes,
     while the forward carried h in fp32 -- so what it computes is not exactly the gradient of the forward that ran.  How far
     off is it?  The fp32 kernels (trunet_gru_fwd / _bwd, exact fp32 hout and gates, pinned by block_gru_bi.npz and the fp64
-    oracle) on the same bf16-representable gi and dhout are the yardstick: relative L2 of dgi, dghn and of the recurrent
+    oracle, and on their own by tests/test_gru_gpu.py) on the same bf16-representable gi and dhout are the yardstick: relative L2 of dgi, dghn and of the recurrent
     weight gradients dW_hh = sum_t dg_t h_{t-1}^T formed from either result (what trunet_bf16_wgrad computes from them).
     Measured (round 4, 1x MI355X, N = 384 x 16 steps): dgi 3.4e-3, dghn 3.8e-3, dW_hh 3.7e-3; bounds at ~3x.  TRUNET_BF16_GRU_IO=0 keeps
     the exact fp32 recurrence between conversion launches."""

@@ -370,6 +370,26 @@ def test_entry_points_reject_null_and_bad_shapes():
     assert lib.trunet_dwconv_fwd(None, None, None, None, None, None, None, 8, 3, 1, 4, 4, 256, 200, None) == EINVAL
 
 
+def test_tgru_entry_points_refuse_before_they_launch():
+    """trunet_tgru_rec_fwd / _bwd: sequence counts that are no multiple of the 32 a workgroup owns, more live sequences than
+    columns, another hidden size, and tensors whose 32-bit row offsets would wrap (4 * 128 * T * SP floats >= 2^31 bytes,
+    i.e. T * SP >= 2^20) are answered on the host -- nothing is launched, so dummy non-null pointers are safe."""
+    from tinyrecurrentunet_amd import _lib
+    lib = _lib.lib()
+    EINVAL, ENOTSUP = _lib.TRUNET_EINVAL, _lib.TRUNET_ENOTSUP
+    P = 0x1000
+    assert lib.trunet_tgru_rec_fwd(None, P, P, P, P, 128, 9, 256, None) == EINVAL
+    assert lib.trunet_tgru_rec_fwd(P, P, P, P, P, 128, 9, 48, None) == EINVAL            # SP % 32
+    assert lib.trunet_tgru_rec_fwd(P, P, P, P, None, 128, 0, 256, None) == EINVAL          # T = 0
+    assert lib.trunet_tgru_rec_fwd(P, P, P, P, P, 64, 9, 256, None) == ENOTSUP           # H other than 128
+    assert lib.trunet_tgru_rec_fwd(P, P, P, P, P, 128, 4096, 256, None) == ENOTSUP       # T * SP = 2^20
+    assert lib.trunet_tgru_rec_bwd(P, P, None, P, P, P, 128, 9, 256, 200, None) == EINVAL  # backward needs the saved gates
+    assert lib.trunet_tgru_rec_bwd(P, P, P, P, P, P, 128, 9, 48, 40, None) == EINVAL     # SP % 32
+    assert lib.trunet_tgru_rec_bwd(P, P, P, P, P, P, 128, 9, 256, 257, None) == EINVAL   # S > SP
+    assert lib.trunet_tgru_rec_bwd(P, P, P, P, P, P, 64, 9, 256, 200, None) == ENOTSUP   # H other than 128
+    assert lib.trunet_tgru_rec_bwd(P, P, P, P, P, P, 128, 4096, 256, 200, None) == ENOTSUP   # T * SP = 2^20
+
+
 def test_bf16_entry_points_reject_null_and_bad_shapes():
     """The trunet_bf16_* family validates on the host like the fp32 entry points (no launch, no GPU needed)."""
     import ctypes as C

@@ -410,6 +410,17 @@ def _block_vs_f64(name, N, ptol=1e-3, zero_floor=2e-2):
             assert _rel(b, dict(ref.named_buffers())[bn_]) < 1e-5, bn_
 
 
+def test_tgru_host_loop_schedule_vs_oracle_f64(monkeypatch):
+    """TRUNET_TGRU_LOOP=1: the time loop as T (conv_gemm, tgru_cell_fwd_kernel) launch pairs forward and
+    (tgru_cell_bwd_kernel, conv_gemm) pairs backward instead of the persistent tgru_rec_* kernels.  Same block, same
+    inputs and the same bounds as test_block_backward_vs_oracle_f64[gru_uni-300]: the fallback schedule must be as right
+    as the persistent one."""
+    import tinyrecurrentunet_amd.engine as E
+    assert E.TGRU_LOOP is False
+    monkeypatch.setattr(E, "TGRU_LOOP", True)
+    _block_vs_f64("gru_uni", 300)
+
+
 def test_saved_activations_are_guarded():
     """activations saved for backward live in the engine's workspace.  A no_grad / eval forward between
     forward and backward must not disturb them (it runs in its own workspace); a second recording forward before the

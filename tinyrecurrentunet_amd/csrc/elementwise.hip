@@ -589,7 +589,9 @@ __global__ __launch_bounds__(256) void gru_cell_kernel(const float* __restrict__
 // ---------------------------------------------------------------- TGRU: sequence-major layout and the time loop's cells
 // frames-last x[c][l][b*T + t]  <->  sequence-major y[c][t][s], s = b*Lf + l (every (utterance, frequency position) is
 // one sequence of the time-recurrent block, network.py:150).  32 x 32 (t, s... ) tiles through LDS; block = (32, 8).
-// to: y = max(sc[c] x + sh[c], lo) (BatchNorm+ReLU of the source, or identity when sc == NULL); y = 0 for s >= S.
+// to: y = max(sc[c] x + sh[c], lo) (BatchNorm+ReLU of the source, or identity when sc == NULL).  The kernel writes the
+// sequences s < S = B*Lf only; y = 0 for s in [S, SP) comes from trunet_to_seq_major, which zero-fills all of y in front of
+// the launch (the padded sequences feed whole-tile GEMMs and the recurrence, so they must be finite).
 __global__ void to_seq_major_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ sc,
                                     const float* __restrict__ sh, int Lf, int T, int B, int NP, int SP, float lo) {
     __shared__ float tl[32][33];

@@ -48,6 +48,9 @@ FUSED_CONVT = os.environ.get("TRUNET_FUSED_CONVT", "1") != "0"
 
 # TGRU time loop as a host loop of (GEMM, cell) launch pairs instead of the persistent kernels (A/B, other H)
 TGRU_LOOP = os.environ.get("TRUNET_TGRU_LOOP", "0") == "1"
+# Debug: fresh workspace buffers that are not asked for as zero are filled with NaN instead of being left as the allocator
+# hands them out, so a kernel that reads memory nobody wrote shows in the results (tests/test_gru_gpu.py).
+POISON_WORKSPACE = os.environ.get("TRUNET_POISON_WORKSPACE", "0") == "1"
 
 # bench.py sets this to a dict to time kernels with HIP events on the launch stream:
 # PROFILE[kernel] = [(start_event, end_event, algorithmic_flops), ...]
@@ -181,10 +184,16 @@ class Workspace:
         self.pending.add(name)
         return clean
 
+    def _new(self, shape, zero, dtype):
+        t = (torch.zeros if zero else torch.empty)(shape, device=self.dev, dtype=dtype)
+        if POISON_WORKSPACE and not zero and t.is_floating_point():
+            t.fill_(float("nan"))
+        return t
+
     def get(self, name, shape, zero=False, dtype=torch.float32):
         t = self.t.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = (torch.zeros if zero else torch.empty)(shape, device=self.dev, dtype=dtype)
+            t = self._new(shape, zero, dtype)
             self.t[name] = t
         elif zero:
             t.zero_()
@@ -195,7 +204,7 @@ class Workspace:
         (re)allocated, not per call."""
         t = self.t.get(name)
         if t is None or t.numel() < numel:
-            t = (torch.zeros if zero else torch.empty)(max(numel, 1), device=self.dev, dtype=dtype)
+            t = self._new(max(numel, 1), zero, dtype)
             self.t[name] = t
             self.pending.discard(name)
         return t
