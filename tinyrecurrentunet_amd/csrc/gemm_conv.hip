@@ -30,7 +30,14 @@ namespace {
 // Pipeline per K-chunk (ring of NB LDS slots, chunk j in slot j % NB):
 //   LDS-DMA (global_load_lds, issued NB chunks ahead, no VGPRs)  ->  in-place prologue pass by the thread that
 //   issued the DMA (one chunk ahead of the MFMAs)  ->  fragment reads + MFMAs.  One raw s_barrier per chunk;
-//   DMA completion is tracked with counted s_waitcnt vmcnt, so NB-1 chunks (16 KiB each) stay in flight.
+//   DMA completion is tracked with counted s_waitcnt vmcnt.  A slot is refilled right after the barrier that frees
+//   it, so while chunk i is multiplied, chunk i+1 is already transformed and chunks i+2 .. i+NB-1 are in flight:
+//   NB-2 chunks (16 KiB each) cross a barrier, and the pass on chunk i+1 found its data requested NB-1 iterations
+//   earlier.  Iteration order for NB >= 3 (and the run-time depth): wait vmcnt((NB-2) LPW), pass on chunk i+1, MFMAs
+//   of chunk i, barrier, refill.  With NB = 2 the chunk to transform was requested a few instructions earlier, at the
+//   end of the previous iteration, and that order would park all eight waves in vmcnt(0) for a whole HBM round trip
+//   in front of the MFMAs.  The depth-2 instances (NBT == 2) therefore run: MFMAs of chunk i, vmcnt(0), pass on
+//   chunk i+1 (the other slot), lgkmcnt(0), barrier, refill -- the round trip runs behind the MFMAs.
 // NW = 4: 128-frame tiles, one wave per SIMD.  NW = 8: 256-frame tiles, the second group of four waves takes the
 // upper 128 frames of every tile -- same per-wave bookkeeping, twice the MFMAs between two barriers, and two waves
 // per SIMD that fill each other's LDS/issue gaps inside the MFMA phase.
@@ -266,13 +273,16 @@ __global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_g
                         if (EPL > 1) ov[r] = *(const bvec*)(a.out + off);
                     }
                 }
-                // prologue pass on the next chunk (its DMA was issued NB-1 chunks ago)
-                if (tf.valid) {
-                    if (EPL > 0 && last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    else wait_vmcnt((NB - 2) * LPW);
-                    transform(tf, tslot);
-                    it_next<KC, FT>(a, tf);
-                    tslot = (tslot + 1 == NB) ? 0 : tslot + 1;
+                // prologue pass on the next chunk (its DMA was issued NB-1 chunks ago).  Depth 2: that DMA left at the end
+                // of the previous iteration, so the pass comes after the MFMAs (below)
+                if constexpr (NBT != 2) {
+                    if (tf.valid) {
+                        if (EPL > 0 && last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        else wait_vmcnt((NB - 2) * LPW);
+                        transform(tf, tslot);
+                        it_next<KC, FT>(a, tf);
+                        tslot = (tslot + 1 == NB) ? 0 : tslot + 1;
+                    }
                 }
                 // fragments of chunk `cur`, then the MFMAs
                 {
@@ -300,6 +310,19 @@ __global__ __launch_bounds__(64 * NW, (EPL == 0 || NW == 8) ? 2 : 1) void conv_g
                         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     }
                     __builtin_amdgcn_sched_group_barrier(0x008, LA * CT, 0);
+                }
+                if constexpr (NBT == 2) {
+                    // Depth 2: the chunk to transform was requested after the previous barrier.  Its round trip runs behind
+                    // the MFMAs above; the wait and the pass touch the other slot and only have to finish before the barrier.
+                    // The fence keeps the wait and the pass's LDS traffic from being scheduled in front of the MFMAs.
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (tf.valid) {
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        transform(tf, tslot);
+                        it_next<KC, FT>(a, tf);
+                        tslot ^= 1;
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // a raw s_barrier does not wait for the pass's LDS writes
                 }
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_s_barrier();
