@@ -466,6 +466,62 @@ def test_bf16_entry_points_reject_null_and_bad_shapes():
     assert lib.trunet_conv_gemm(g, None) == ENOTSUP
 
 
+def test_convt_bwd_entry_points_refuse_before_they_launch():
+    """trunet_convt_bwd and trunet_bf16_convt_bwd answer on the host, before any HIP call (dummy non-null pointers are
+    safe): TRUNET_EINVAL for a missing required pointer (b_partials alone is optional), NP that is no multiple of the
+    frame tile (128 fp32, 64 bf16), N outside 1 .. NP, Lin <= 0, w_numel <= 0, pad != S / 2 and an Lout that does not
+    follow from (Lin, K, S); TRUNET_ENOTSUP for channel counts other than 64, for a (K, S) without an instance, and --
+    fp32 entry, 32-bit buffer-store offsets -- for 36 channel rows of the gradient tensor at or above 2 GiB."""
+    from tinyrecurrentunet_amd import _lib
+    lib = _lib.lib()
+    EINVAL, ENOTSUP = _lib.TRUNET_EINVAL, _lib.TRUNET_ENOTSUP
+    P = 0x1000
+    F32_PTRS = ("dy", "z", "ca", "cb", "cc", "src", "s_scale", "s_shift", "s_mean", "W", "dsrc", "partials", "w_partials")
+    B16_PTRS = tuple("wfragT" if n == "W" else n for n in F32_PTRS)
+
+    def make(cls, ptrs, **kw):
+        a = cls()
+        a.NP, a.N, a.Lin, a.K, a.S, a.Ci, a.Co, a.w_numel, a.b_stride, a.b_off = 256, 200, 4, 3, 2, 64, 64, 64 * 64 * 5, 64, 0
+        for n in ptrs + ("b_partials",):
+            setattr(a, n, P)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        if "pad" not in kw:
+            a.pad = a.S // 2
+        if "Lout" not in kw:
+            a.Lout = (a.Lin - 1) * a.S - 2 * a.pad + a.K
+        return a
+
+    for fn, cls, ptrs, tile in ((lib.trunet_convt_bwd, _lib.ConvtBwdArgs, F32_PTRS, 128),
+                                (lib.trunet_bf16_convt_bwd, _lib.BConvtArgs, B16_PTRS, 64)):
+        assert fn(None, None) == EINVAL
+        for n in ptrs:
+            assert fn(make(cls, ptrs, **{n: None}), None) == EINVAL, n
+        assert fn(make(cls, ptrs, NP=256 + tile // 2, N=200), None) == EINVAL          # NP % tile
+        assert fn(make(cls, ptrs, NP=0, N=0), None) == EINVAL
+        for N in (0, -3, 257):
+            assert fn(make(cls, ptrs, N=N), None) == EINVAL, N                          # N <= 0, N > NP
+        for Lin in (0, -1):
+            assert fn(make(cls, ptrs, Lin=Lin), None) == EINVAL, Lin
+        for w_numel in (0, -4096):
+            assert fn(make(cls, ptrs, w_numel=w_numel), None) == EINVAL, w_numel
+        for K, S in ((3, 1), (3, 2), (5, 2)):
+            assert fn(make(cls, ptrs, K=K, S=S, pad=S // 2 + 1), None) == EINVAL          # pad != S / 2 (Lout follows the pad given)
+            assert fn(make(cls, ptrs, K=K, S=S, pad=1 - S // 2), None) == EINVAL
+            good = make(cls, ptrs, K=K, S=S).Lout
+            for Lout in (good - 1, good + 1, 0):
+                assert fn(make(cls, ptrs, K=K, S=S, Lout=Lout), None) == EINVAL, (K, S, Lout)
+        for Ci, Co in ((32, 64), (64, 32), (128, 128), (8, 8)):
+            assert fn(make(cls, ptrs, Ci=Ci, Co=Co), None) == ENOTSUP, (Ci, Co)
+        for K, S in ((5, 1), (7, 2)):
+            assert fn(make(cls, ptrs, K=K, S=S), None) == ENOTSUP, (K, S)               # consistent Lout, no instance
+    # fp32 entry: Lin * NP * 4 bytes * 36 rows >= 2^31
+    big = make(_lib.ConvtBwdArgs, F32_PTRS, Lin=128, NP=116608, N=116608, K=3, S=1)
+    assert 128 * 116608 * 4 * 36 >= 2 ** 31 and 116608 % 128 == 0
+    assert lib.trunet_convt_bwd(big, None) == ENOTSUP
+    assert lib.trunet_convt_bwd_nparts() > 0 and lib.trunet_bf16_convt_bwd_nparts() == 2 * lib.trunet_conv_wgrad_nparts()
+
+
 def test_bf16_kernel_name_mirror_and_precision_switch():
     """engine_bf16._bgemm_name mirrors trunet_bf16_gemm's dispatch (bench.py matches it against rocprofv3 names);
     TRUNet(precision=...) validates its argument without touching the GPU"""
