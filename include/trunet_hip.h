@@ -206,13 +206,17 @@ int trunet_reduce_partials(float* out, const float* partials, int nparts, int nu
 /* BatchNorm1d training statistics -> affine (network.py:31,39,51,65,72 ...; torch semantics:
  * biased variance for normalisation, unbiased for running_var, momentum 0.1, eps 1e-5).
  * partials: [nparts][C][2] = sum, sumsq.  Writes scale = gamma*rstd, shift = beta - mean*scale,
- * mean, rstd; updates running_mean / running_var in place when non-NULL and adds 1 to the int64 counter
- * num_batches_tracked (BatchNorm1d's buffer) when non-NULL. */
+ * mean, rstd; updates running_mean / running_var in place when non-NULL (both or neither; count == 1 takes the biased
+ * variance) and adds 1 to the int64 counter num_batches_tracked (BatchNorm1d's buffer) when non-NULL.  Both finalize calls
+ * leave the partial rows they consumed exactly +0, and return TRUNET_EINVAL for C, nparts or count <= 0.
+ * The variance is sumsq / count - mean^2, in double but from the producers' fp32 partial sums: its absolute error is up to
+ * 2^-24 (sum_g |sumsq_g| + 2 |mean| sum_g |sum_g|) / count, i.e. about 3 x 2^-24 mean^2 ("What pins the
+ * BatchNorm chain"). */
 int trunet_bn_finalize_fwd(float* partials, int nparts, int C, double count, const float* gamma,
                            const float* beta, float eps, float momentum, float* running_mean,
                            float* running_var, float* scale, float* shift, float* mean, float* rstd,
                            int64_t* num_batches_tracked, void* stream);
-/* eval mode: scale/shift from running statistics */
+/* eval mode: scale/shift from running statistics (TRUNET_EINVAL for C <= 0) */
 int trunet_bn_eval_affine(int C, const float* gamma, const float* beta, const float* running_mean,
                           const float* running_var, float eps, float* scale, float* shift, void* stream);
 /* BatchNorm backward reduction: partials [nparts][C][2] = sum(dy), sum(dy*(z-mean)).

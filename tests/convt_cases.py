@@ -261,14 +261,15 @@ def launch(c, inst, **kw):
 
 
 # ---------------------------------------------------------------------------------------------- comparison and report
-def report(line):
-    """one line per case and instance: printed, and appended to parity_convt.txt in the directory TRUNET_PARITY_DIR names
-    (relative to the repository root), where that is set and the directory exists"""
+def report(line, name="parity_convt.txt"):
+    """one line per case and instance: printed, and appended to the file `name` in the directory TRUNET_PARITY_DIR names
+    (relative to the repository root), where that is set and the directory exists.  The one writer of the parity files of
+    the per-kernel pins (tests/gru_cases.py and tests/bn_cases.py call it with their file names)."""
     print(line)
     out_dir = os.environ.get("TRUNET_PARITY_DIR")
     out_dir = os.path.join(ROOT, out_dir) if out_dir else None
     if out_dir and os.path.isdir(out_dir):
-        with open(os.path.join(out_dir, "parity_convt.txt"), "a") as f:
+        with open(os.path.join(out_dir, name), "a") as f:
             f.write(line + "\n")
 
 

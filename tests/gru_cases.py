@@ -153,12 +153,8 @@ def report(line):
     ne = os.environ.get("TRUNET_GRU_NE")
     if ne:
         line = "[TRUNET_GRU_NE=%s] %s" % (ne, line)
-    print(line)
-    out_dir = os.environ.get("TRUNET_PARITY_DIR")
-    out_dir = os.path.join(ROOT, out_dir) if out_dir else None
-    if out_dir and os.path.isdir(out_dir):
-        with open(os.path.join(out_dir, "parity_gru.txt"), "a") as f:
-            f.write(line + "\n")
+    from convt_cases import report as write
+    write(line, "parity_gru.txt")
 
 
 def compare(tag, items):

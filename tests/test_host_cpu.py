@@ -370,6 +370,69 @@ def test_entry_points_reject_null_and_bad_shapes():
     assert lib.trunet_dwconv_fwd(None, None, None, None, None, None, None, 8, 3, 1, 4, 4, 256, 200, None) == EINVAL
 
 
+def test_bn_chain_entry_points_refuse_before_they_launch():
+    """The BatchNorm bookkeeping and block-boundary entry points (elementwise.hip, trunet_reduce_partials in gemm_conv.hip)
+    answer NULLs, half-given pointer pairs and impossible extents on the host -- nothing is launched, so dummy non-null
+    pointers are safe.  trunet_bn_finalize_bwd used to check neither C, nparts nor count, trunet_bn_eval_affine not C (C = 0
+    became a zero-size launch) and trunet_bn_finalize_fwd took count <= 0 (NaN scales)."""
+    import ctypes as C
+    from tinyrecurrentunet_amd import _lib
+    lib = _lib.lib()
+    EINVAL, ENOTSUP = _lib.TRUNET_EINVAL, _lib.TRUNET_ENOTSUP
+    P, d = 0x1000, C.c_double
+    nan = float("nan")
+
+    def fwd(partials=P, nparts=16, Cn=8, count=100.0, gamma=P, beta=P, rm=P, rv=P, scale=P, shift=P, mean=P, rstd=P, nbt=P):
+        return lib.trunet_bn_finalize_fwd(partials, nparts, Cn, d(count), gamma, beta, 1e-5, 0.1, rm, rv, scale, shift, mean,
+                                          rstd, nbt, None)
+    for k in ("partials", "gamma", "beta", "scale", "shift", "mean", "rstd"):
+        assert fwd(**{k: None}) == EINVAL, k
+    assert fwd(rv=None) == EINVAL and fwd(rm=None) == EINVAL                  # running_mean without running_var, and back
+    assert fwd(nparts=0) == EINVAL and fwd(Cn=0) == EINVAL and fwd(Cn=-1) == EINVAL
+    assert fwd(count=0.0) == EINVAL and fwd(count=-1.0) == EINVAL and fwd(count=nan) == EINVAL
+
+    def bwd(partials=P, nparts=16, Cn=8, count=100.0, gamma=P, mean=P, rstd=P, dgamma=P, dbeta=P, ca=P, cb=P, cc=P):
+        return lib.trunet_bn_finalize_bwd(partials, nparts, Cn, d(count), gamma, mean, rstd, dgamma, dbeta, ca, cb, cc, None)
+    for k in ("partials", "gamma", "mean", "rstd", "dgamma", "dbeta", "ca", "cb", "cc"):
+        assert bwd(**{k: None}) == EINVAL, k
+    assert bwd(nparts=0) == EINVAL and bwd(nparts=-3) == EINVAL and bwd(Cn=0) == EINVAL and bwd(Cn=-1) == EINVAL
+    assert bwd(count=0.0) == EINVAL and bwd(count=-2.0) == EINVAL and bwd(count=nan) == EINVAL
+
+    def ev(Cn=8, gamma=P, beta=P, rm=P, rv=P, scale=P, shift=P):
+        return lib.trunet_bn_eval_affine(Cn, gamma, beta, rm, rv, 1e-5, scale, shift, None)
+    for k in ("gamma", "beta", "rm", "rv", "scale", "shift"):
+        assert ev(**{k: None}) == EINVAL, k
+    assert ev(Cn=0) == EINVAL and ev(Cn=-5) == EINVAL
+
+    def relu(dy=P, z=P, sc=P, sh=P, mean=P, partials=P, Cn=4, L=4, NP=256, N=200):
+        return lib.trunet_relu_bwd_stats(dy, z, sc, sh, mean, partials, Cn, L, NP, N, None)
+    assert relu(dy=None) == EINVAL and relu(z=None) == EINVAL
+    assert relu(sh=None) == EINVAL and relu(sc=None) == EINVAL                # scale without shift, and back
+    assert relu(partials=None) == EINVAL and relu(mean=None) == EINVAL        # mean without partials, and back
+    assert relu(NP=200) == EINVAL and relu(NP=128, N=129) == EINVAL           # NP % 128, NP < N
+    assert relu(Cn=0) == EINVAL and relu(L=0) == EINVAL and relu(N=0) == EINVAL and relu(NP=0) == EINVAL
+
+    def ffl(x=P, y=P, N=200, Cn=4, L=4, NP=256, scale=P, shift=P):
+        return lib.trunet_from_frames_last_affine(x, y, N, Cn, L, NP, scale, shift, 1, None)
+    for k in ("x", "y", "scale", "shift"):
+        assert ffl(**{k: None}) == EINVAL, k
+    assert ffl(N=257) == EINVAL and ffl(N=0) == EINVAL and ffl(Cn=0) == EINVAL and ffl(L=0) == EINVAL and ffl(L=-2) == EINVAL
+
+    def cf(x=P, w=P, b=P, y=P, Cin=4, Cout=64, K=5, S=2, Lin=257, Lout=128, NP=256):
+        return lib.trunet_conv_first_fwd(x, w, b, y, Cin, Cout, K, S, Lin, Lout, NP, None)
+    for k in ("x", "w", "b", "y"):
+        assert cf(**{k: None}) == EINVAL, k
+    assert cf(NP=200) == EINVAL and cf(NP=0) == EINVAL
+    assert cf(Cout=0) == EINVAL and cf(S=0) == EINVAL and cf(Lin=0) == EINVAL and cf(Lout=0) == EINVAL and cf(Lout=-1) == EINVAL
+    assert cf(K=3) == ENOTSUP and cf(K=7) == ENOTSUP and cf(Cin=2) == ENOTSUP and cf(Cin=5) == ENOTSUP and cf(Cin=64) == ENOTSUP
+
+    assert lib.trunet_reduce_partials(None, P, 4, 16, 0, None) == EINVAL and lib.trunet_reduce_partials(P, None, 4, 16, 0, None) == EINVAL
+    assert lib.trunet_reduce_partials(P, P, 0, 16, 0, None) == EINVAL and lib.trunet_reduce_partials(P, P, 4, 0, 1, None) == EINVAL
+    assert lib.trunet_reduce_partials(P, P, -1, 16, 0, None) == EINVAL and lib.trunet_reduce_partials(P, P, 4, -16, 1, None) == EINVAL
+    assert lib.trunet_sumsq(None, 16, P, None) == EINVAL and lib.trunet_sumsq(P, 16, None, None) == EINVAL
+    assert lib.trunet_sumsq(P, 0, P, None) == EINVAL and lib.trunet_sumsq(P, -4, P, None) == EINVAL
+
+
 def test_tgru_entry_points_refuse_before_they_launch():
     """trunet_tgru_rec_fwd / _bwd: sequence counts that are no multiple of the 32 a workgroup owns, more live sequences than
     columns, another hidden size, and tensors whose 32-bit row offsets would wrap (4 * 128 * T * SP floats >= 2^31 bytes,

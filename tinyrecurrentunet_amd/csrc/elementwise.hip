@@ -954,7 +954,7 @@ extern "C" int trunet_tgru_cell_bwd(float* dhs, const float* carry, const float*
 
 extern "C" int trunet_from_frames_last_affine(const float* x, float* y, int N, int C, int L, int NP, const float* scale,
                                               const float* shift, int relu, void* stream) {
-    if (!x || !y || !scale || !shift || N <= 0 || NP < N) return TRUNET_EINVAL;
+    if (!x || !y || !scale || !shift || N <= 0 || NP < N || C <= 0 || L <= 0) return TRUNET_EINVAL;
     int R = C * L;
     hipLaunchKernelGGL(from_frames_last_affine_kernel, dim3((NP + 31) / 32, (R + 31) / 32), dim3(32, 8), 0, ST, x, y, N, R,
                        NP, L, scale, shift, relu ? 0.f : -3.0e38f);
@@ -963,7 +963,7 @@ extern "C" int trunet_from_frames_last_affine(const float* x, float* y, int N, i
 
 extern "C" int trunet_conv_first_fwd(const float* x, const float* w, const float* b, float* y, int Cin, int Cout, int K,
                                      int S, int Lin, int Lout, int NP, void* stream) {
-    if (!x || !w || !b || !y || (NP % 128)) return TRUNET_EINVAL;
+    if (!x || !w || !b || !y || Cout <= 0 || S <= 0 || Lin <= 0 || Lout <= 0 || NP <= 0 || (NP % 128)) return TRUNET_EINVAL;
     dim3 grid(NP / 128, (Lout + 7) / 8), block(32, 8);
     if (K == 5 && Cin == 3) hipLaunchKernelGGL((conv_first_kernel<3, 5>), grid, block, 0, ST, x, w, b, y, Cout, S, Lin, Lout, NP);
     else if (K == 5 && Cin == 4) hipLaunchKernelGGL((conv_first_kernel<4, 5>), grid, block, 0, ST, x, w, b, y, Cout, S, Lin, Lout, NP);
@@ -1069,6 +1069,7 @@ extern "C" int trunet_bn_finalize_fwd(float* partials, int nparts, int C, double
                                       float* running_var, float* scale, float* shift, float* mean, float* rstd,
                                       int64_t* num_batches_tracked, void* stream) {
     if (!partials || !gamma || !beta || !scale || !shift || !mean || !rstd || C <= 0 || nparts <= 0) return TRUNET_EINVAL;
+    if (!(count > 0.0)) return TRUNET_EINVAL;          // count <= 0 (or NaN) would write NaN scales
     if ((running_mean == nullptr) != (running_var == nullptr)) return TRUNET_EINVAL;
     hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(C), dim3(256), 0, ST, partials, nparts, C, count, gamma, beta, eps,
                        momentum, running_mean, running_var, scale, shift, mean, rstd, (long long*)num_batches_tracked);
@@ -1077,7 +1078,7 @@ extern "C" int trunet_bn_finalize_fwd(float* partials, int nparts, int C, double
 
 extern "C" int trunet_bn_eval_affine(int C, const float* gamma, const float* beta, const float* running_mean,
                                      const float* running_var, float eps, float* scale, float* shift, void* stream) {
-    if (!gamma || !beta || !running_mean || !running_var || !scale || !shift) return TRUNET_EINVAL;
+    if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || C <= 0) return TRUNET_EINVAL;
     hipLaunchKernelGGL(bn_eval_affine_kernel, dim3((C + 127) / 128), dim3(128), 0, ST, C, gamma, beta, running_mean,
                        running_var, eps, scale, shift);
     return trunet_launch_status();
@@ -1087,6 +1088,7 @@ extern "C" int trunet_bn_finalize_bwd(float* partials, int nparts, int C, double
                                       const float* mean, const float* rstd, float* dgamma, float* dbeta, float* ca,
                                       float* cb, float* cc, void* stream) {
     if (!partials || !gamma || !mean || !rstd || !dgamma || !dbeta || !ca || !cb || !cc) return TRUNET_EINVAL;
+    if (C <= 0 || nparts <= 0 || !(count > 0.0)) return TRUNET_EINVAL;
     hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(C), dim3(256), 0, ST, partials, nparts, C, count, gamma, mean, rstd,
                        dgamma, dbeta, ca, cb, cc);
     return trunet_launch_status();
