@@ -335,7 +335,11 @@ int trunet_pcen(const float* mag, float* out, int B, int T, int out_stride, floa
                 float delta, float r, void* stream);
 /* R7 glue (util.py:217-235 intent; phm.py:31-45; dataset.py:182-203,293-296): net output (B*T, 8, 257) ->
  * phase-aware mask -> rect-window iSTFT -> audio (B, L), L = 128 (T-1).  frames: scratch (B, T, 512).
- * With clean != NULL also writes per-block sums of |audio - clean| (util.py:239) to l1_partials. */
+ * With clean != NULL also writes per-block sums of |audio - clean| (util.py:239) to l1_partials
+ * (trunet_mask_istft_l1_nparts(B, L) = B * ceil(L / 256) floats; the last block of L = 128 * odd sums 128 samples).
+ * Arguments: B >= 1, T >= 2, L == 128 (T-1); anything else is TRUNET_EINVAL before a launch.
+ * Backward: a phase pair that is exactly (0, 0) gets gradient 0 (c2 = c3 = 0 zeroes g2, g3; c6 = c7 = 0 zeroes g6, g7),
+ * clamp(c0, -1, 1) passes its gradient on the closed interval, channels 1, 4, 5 get 0. */
 int trunet_mask_istft_fwd(const float* net_out, float* frames, float* audio, const float* clean,
                           float* l1_partials, const float* tw512, int B, int T, int L, float beta, void* stream);
 int trunet_mask_istft_l1_nparts(int B, int L);
@@ -343,14 +347,20 @@ int trunet_mask_istft_bwd(const float* g_audio, const float* net_out, float* g_n
                           int T, int L, float beta, void* stream);
 /* g[i] = scale[0] * sign(den[i] - clean[i])  (backward of nn.L1Loss, util.py:239) */
 int trunet_l1_grad(const float* den, const float* clean, const float* scale, float* g, int64_t n, void* stream);
-/* out[c] = sum_g partials[g*ncols + c] in fp64 */
+/* out[c] = sum_g partials[g*ncols + c] in fp64 (one fp32 rounding of the sum); nparts, ncols >= 1 */
 int trunet_reduce_cols(const float* partials, int nparts, int ncols, float* out, void* stream);
 /* One resolution of MultiResolutionSTFTLoss (stft_loss.py:9-113): win = Hann(win_length) zero-padded to n,
  * frames = 1 + L/hop.  fwd: partials[(b*frames + f)][3] = sum (|Y|-|X|)^2, sum |Y|^2, sum |log|Y| - log|X||
- * with |.| = sqrt(clamp(re^2+im^2, 1e-7)). */
+ * with |.| = sqrt(clamp(re^2+im^2, 1e-7)).
+ * Arguments of every STFT entry point (this one, _bwd_gather, _fwdgrad, trunet_stft_mag, trunet_stft_mag_bwd, and per
+ * resolution trunet_loss_grad_gather): n a power of two, 8 <= n <= 2048 (the (2n + n/2) * 8 bytes of dynamic LDS stay
+ * inside the 64 KB a kernel gets without raising its limit; n = 4096 is refused, not launched), L > n/2, hop >= 1,
+ * 1 <= win_length <= n, B >= 1; anything else is TRUNET_EINVAL before a launch.
+ * A frame whose windowed x and y are bit-identical has |Y| = |X| exactly (not the two results of the shared transform,
+ * whose roundings differ): its first and third sums are exactly 0 and it contributes no loss gradient. */
 int trunet_stft_loss_fwd(const float* x, const float* y, const float* win, const float* tw, float* partials,
                          int B, int L, int n, int hop, void* stream);
-/* bwd: d loss / d x -> gx (B, L) given coef[0] = g_sc*lambda_sc/(nres*sqrt(S1)*sqrt(S2)), coef[1] =
+/* bwd: d loss / d x -> gx (B, L) given coef[0] = g_sc*lambda_sc/(nres*sqrt(S1)*sqrt(S2)) (0 at S1 == 0), coef[1] =
  * g_mag*lambda_mag/(nres*count).  No float atomics: the windowed frame gradients go to `frames` (B, frames, win_length:
  * the window's support, centred in n) and a gather sums them per sample; gx is written (not accumulated), deterministic. */
 int trunet_stft_loss_bwd_gather(const float* x, const float* y, const float* win, const float* tw, const float* coef,
@@ -494,8 +504,11 @@ typedef struct trunet_loss_args {
 /* One launch: every column sum in fp64 and the scalar algebra of util.py:239-250 / stft_loss.py:151-166:
  * loss_out[0] = l1 + stft_lambda * (sc_lambda * sum_i sqrt(S1_i)/sqrt(S2_i) + mag_lambda * sum_i S3_i/count_i) / nres;
  * vals (>= 5 + 2 nres floats): [0] loss [1] l1 [2] stft_sc term [3] stft_mag term [4] 1/(B L) [5+2i] c_sc_i [6+2i] c_mag_i
- * (the backward coefficients for an upstream gradient of 1).  scratch: trunet_loss_scratch_bytes() bytes, ZERO on first use
- * (the kernel leaves it zero). */
+ * (the backward coefficients for an upstream gradient of 1); c_sc_i is 0 where S1_i == 0 (x equals y in every bin: the
+ * gradient of sqrt(S1)/sqrt(S2) is 0 there, as torch's norm has it, not the inf of 1/(sqrt(S1) sqrt(S2))).
+ * scratch: trunet_loss_scratch_bytes() bytes, ZERO on first use (the kernel leaves ALL of it zero).
+ * Arguments: n_l1 >= 1, l1_count > 0, 0 <= nres <= TRUNET_MAX_RES, per resolution nrows >= 1 and count > 0 (a NaN count
+ * is refused); anything else is TRUNET_EINVAL before a launch. */
 size_t trunet_loss_scratch_bytes(void);
 int trunet_loss_finalize(const trunet_loss_args* a, float* loss_out, float* vals, void* scratch, void* stream);
 typedef struct trunet_loss_gather_args {
@@ -505,7 +518,8 @@ typedef struct trunet_loss_gather_args {
     int32_t nres, _pad;
 } trunet_loss_gather_args;
 /* d loss / d audio (B, L) in one deterministic gather: g_loss[0] * (vals[4] * sign(audio - clean) + sum_i (vals[5+2i] *
- * OLA_i(fr_sc_i) + vals[6+2i] * OLA_i(fr_mag_i))) -- autograd of nn.L1Loss (util.py:239) + stft_loss.py:9-113. */
+ * OLA_i(fr_sc_i) + vals[6+2i] * OLA_i(fr_mag_i))) -- autograd of nn.L1Loss (util.py:239) + stft_loss.py:9-113.
+ * sign(0) = 0; 0 <= nres <= TRUNET_MAX_RES, B, L >= 1, and per resolution the STFT argument ranges above. */
 int trunet_loss_grad_gather(const trunet_loss_gather_args* a, const float* audio, const float* clean, const float* vals,
                             const float* g_loss, float* g_audio, int B, int L, void* stream);
 /* stft() of stft_loss.py:9-30: magnitudes sqrt(clamp(re^2+im^2, 1e-7)) of the Hann-windowed, centre/reflect-padded STFT

@@ -433,6 +433,90 @@ def test_bn_chain_entry_points_refuse_before_they_launch():
     assert lib.trunet_sumsq(P, 0, P, None) == EINVAL and lib.trunet_sumsq(P, -4, P, None) == EINVAL
 
 
+def test_loss_tail_entry_points_refuse_before_they_launch():
+    """The loss tail of fft.hip (mask + iSTFT, L1, the STFT-loss kernels, the fused loss algebra, the gradient gather) answers
+    impossible arguments on the host -- nothing is launched, so dummy non-null pointers are safe.  The STFT size is a power of
+    two from 8 to 2048: n = 4096 needs 80 KB of dynamic LDS, which no launch here asks for, and used to be accepted (as was
+    any n up to 2^31 - 1 by trunet_loss_grad_gather); a NaN count passed `count <= 0`."""
+    import ctypes as C
+    from tinyrecurrentunet_amd import _lib
+    lib = _lib.lib()
+    EINVAL = _lib.TRUNET_EINVAL
+    P = 0x1000
+    nan = float("nan")
+
+    stft = {
+        "fwd": lambda B=2, L=700, n=512, hop=50, wl=240: lib.trunet_stft_loss_fwd(P, P, P, P, P, B, L, n, hop, None),
+        "mag": lambda B=2, L=700, n=512, hop=50, wl=240: lib.trunet_stft_mag(P, P, P, P, P, P, B, L, n, hop, None),
+        "bwd_gather": lambda B=2, L=700, n=512, hop=50, wl=240: lib.trunet_stft_loss_bwd_gather(P, P, P, P, P, P, P, B, L, n, hop, wl, None),
+        "fwdgrad": lambda B=2, L=700, n=512, hop=50, wl=240: lib.trunet_stft_loss_fwdgrad(P, P, P, P, P, P, P, B, L, n, hop, wl, None),
+        "mag_bwd": lambda B=2, L=700, n=512, hop=50, wl=240: lib.trunet_stft_mag_bwd(P, P, P, P, P, P, B, L, n, hop, wl, None),
+    }
+
+    def gather(nres=1, B=2, L=700, n=512, hop=50, wl=240, fr=P, which=0):
+        a = _lib.LossGatherArgs()
+        a.nres = nres
+        for i in range(max(0, min(nres, _lib.MAX_RES))):
+            a.fr_sc[i], a.fr_mag[i], a.n[i], a.hop[i], a.win_length[i] = P, P, 512, 50, 240
+        if 0 <= which < _lib.MAX_RES:
+            a.fr_sc[which], a.n[which], a.hop[which], a.win_length[which] = fr, n, hop, wl
+        return lib.trunet_loss_grad_gather(C.byref(a), P, P, P, P, P, B, L, None)
+    stft["gather"] = gather
+    for name, f in stft.items():
+        for n in (1000, 24, 0, -512, 4, 2, 4096, 8192, 1 << 30, 2 ** 31 - 1):         # no power of two; < 8; above the maximum
+            assert f(n=n, wl=1, L=2 ** 30) == EINVAL, (name, n)
+        assert f(L=256) == EINVAL and f(L=0) == EINVAL and f(n=2048, wl=1200, L=1024) == EINVAL, name      # L <= n/2
+        assert f(hop=0) == EINVAL and f(hop=-50) == EINVAL, name
+        assert f(B=0) == EINVAL and f(B=-2) == EINVAL, name
+        if name not in ("fwd", "mag"):
+            assert f(wl=0) == EINVAL and f(wl=-1) == EINVAL and f(wl=513) == EINVAL, name                  # outside 1 .. n
+    assert gather(nres=-1) == EINVAL and gather(nres=9) == EINVAL
+    assert gather(nres=3, which=2, n=4096) == EINVAL and gather(nres=3, which=2, fr=None) == EINVAL
+    assert gather(L=0) == EINVAL and gather(L=-700) == EINVAL
+
+    def fin(n_l1=6, l1_count=1400.0, nres=2, nrows=30, count=7710.0, part=P, l1=P, which=1):
+        a = _lib.LossArgs()
+        a.l1_partials, a.n_l1, a.nres, a.l1_count = l1, n_l1, nres, l1_count
+        a.sc_lambda, a.mag_lambda, a.stft_lambda = 0.5, 0.5, 1.0
+        for i in range(max(0, min(nres, _lib.MAX_RES))):
+            a.parts[i], a.nrows[i], a.count[i] = P, 30, 7710.0
+        if 0 <= which < _lib.MAX_RES:
+            a.parts[which], a.nrows[which], a.count[which] = part, nrows, count
+        return lib.trunet_loss_finalize(C.byref(a), P, P, P, None)
+    assert fin(nres=-1) == EINVAL and fin(nres=9) == EINVAL
+    assert fin(n_l1=0) == EINVAL and fin(n_l1=-6) == EINVAL and fin(l1=None) == EINVAL
+    assert fin(l1_count=0.0) == EINVAL and fin(l1_count=-1.0) == EINVAL and fin(l1_count=nan) == EINVAL
+    assert fin(nrows=0) == EINVAL and fin(nrows=-30) == EINVAL and fin(part=None) == EINVAL
+    assert fin(count=0.0) == EINVAL and fin(count=-2.0) == EINVAL and fin(count=nan) == EINVAL
+    a = _lib.LossArgs()
+    a.l1_partials, a.n_l1, a.l1_count = P, 6, 1400.0
+    assert lib.trunet_loss_finalize(C.byref(a), None, P, P, None) == EINVAL and lib.trunet_loss_finalize(C.byref(a), P, None, P, None) == EINVAL
+    assert lib.trunet_loss_finalize(C.byref(a), P, P, None, None) == EINVAL and lib.trunet_loss_finalize(None, P, P, P, None) == EINVAL
+
+    def mfwd(B=3, T=5, L=512):
+        return lib.trunet_mask_istft_fwd(P, P, P, P, P, P, B, T, L, 0.5, None)
+
+    def mbwd(B=3, T=5, L=512):
+        return lib.trunet_mask_istft_bwd(P, P, P, P, B, T, L, 0.5, None)
+    for f in (mfwd, mbwd):
+        assert f(T=1, L=0) == EINVAL and f(T=0, L=-128) == EINVAL and f(T=-3, L=512) == EINVAL              # T < 2
+        assert f(L=511) == EINVAL and f(L=640) == EINVAL and f(T=6) == EINVAL and f(L=0) == EINVAL          # L != 128 (T - 1)
+        assert f(B=0) == EINVAL and f(B=-1) == EINVAL
+    assert lib.trunet_mask_istft_fwd(None, P, P, P, P, P, 3, 5, 512, 0.5, None) == EINVAL
+    assert lib.trunet_mask_istft_fwd(P, None, P, P, P, P, 3, 5, 512, 0.5, None) == EINVAL
+    assert lib.trunet_mask_istft_fwd(P, P, None, P, P, P, 3, 5, 512, 0.5, None) == EINVAL
+    assert lib.trunet_mask_istft_fwd(P, P, P, P, P, None, 3, 5, 512, 0.5, None) == EINVAL
+    for k in range(4):
+        args = [P, P, P, P]
+        args[k] = None
+        assert lib.trunet_mask_istft_bwd(*args, 3, 5, 512, 0.5, None) == EINVAL, k
+        assert lib.trunet_l1_grad(*args, 100, None) == EINVAL, k
+    assert lib.trunet_l1_grad(P, P, P, P, 0, None) == EINVAL and lib.trunet_l1_grad(P, P, P, P, -100, None) == EINVAL
+    assert lib.trunet_reduce_cols(None, 10, 3, P, None) == EINVAL and lib.trunet_reduce_cols(P, 10, 3, None, None) == EINVAL
+    assert lib.trunet_reduce_cols(P, 0, 3, P, None) == EINVAL and lib.trunet_reduce_cols(P, -10, 3, P, None) == EINVAL
+    assert lib.trunet_reduce_cols(P, 10, 0, P, None) == EINVAL and lib.trunet_reduce_cols(P, 10, -3, P, None) == EINVAL
+
+
 def test_tgru_entry_points_refuse_before_they_launch():
     """trunet_tgru_rec_fwd / _bwd: sequence counts that are no multiple of the 32 a workgroup owns, more live sequences than
     columns, another hidden size, and tensors whose 32-bit row offsets would wrap (4 * 128 * T * SP floats >= 2^31 bytes,

@@ -805,8 +805,13 @@ __global__ __launch_bounds__(256) void stream_feed_ola_kernel(const float* __res
 // signals are requested before the first one is used: as a `for (i = tid; i < n; i += 256)` loop of unknown trip count
 // hipcc issued load, wait, LDS store per iteration -- eight L2 round trips in a row at n = 2048, most of the ~12 us a
 // block of these kernels took (round 3).  NI = 0: any other n (runtime loops).
+// Returns whether this thread staged a tap at which the two windowed signals differ: a frame in which NO thread did holds the
+// same data twice, and its two spectra are equal in exact arithmetic -- but not out of the shared transform, whose roundings
+// for bin k and bin n - k differ.  The kernels give such a frame |Y| = |X| (stft_same_frame), so that x == y means ym == xm and
+// sign(log |X| - log |Y|) == 0 bit for bit, as it does for torch, and not a rounding-sized S1 under a square root and a
+// random sign per bin.  Frames that differ anywhere take the arithmetic they always took.
 template <int NI, bool YZERO>
-__device__ __forceinline__ void stft_stage_frame(cpx* sa, cpx* stw, const float* __restrict__ xb,
+__device__ __forceinline__ bool stft_stage_frame(cpx* sa, cpx* stw, const float* __restrict__ xb,
                                                  const float* __restrict__ yb, const float* __restrict__ win,
                                                  const cpx* __restrict__ tw, int f, int hop, int n, int L) {
     if constexpr (NI > 0) {
@@ -822,18 +827,39 @@ __device__ __forceinline__ void stft_stage_frame(cpx* sa, cpx* stw, const float*
         }
 #pragma unroll
         for (int it = 0; it < NI / 2; ++it) t[it] = tw[threadIdx.x + 256 * it];
+        bool diff = false;
 #pragma unroll
-        for (int it = 0; it < NI; ++it) sa[threadIdx.x + 256 * it] = make_float2(w[it] * vx[it], w[it] * vy[it]);
+        for (int it = 0; it < NI; ++it) {
+            const cpx z = make_float2(w[it] * vx[it], w[it] * vy[it]);
+            diff |= (z.x != z.y);
+            sa[threadIdx.x + 256 * it] = z;
+        }
 #pragma unroll
         for (int it = 0; it < NI / 2; ++it) stw[threadIdx.x + 256 * it] = t[it];
+        return diff;
     } else {
+        bool diff = false;
         for (int i = threadIdx.x; i < n / 2; i += 256) stw[i] = tw[i];
         for (int i = threadIdx.x; i < n; i += 256) {
             const int j = reflect_idx(f * hop + i - n / 2, L);
             const float w = win[i];
-            sa[i] = make_float2(w * xb[j], YZERO ? 0.f : w * yb[j]);
+            const cpx z = make_float2(w * xb[j], YZERO ? 0.f : w * yb[j]);
+            diff |= (z.x != z.y);
+            sa[i] = z;
         }
+        return diff;
     }
+}
+
+template <bool V> struct SameFrame { static constexpr bool value = V; };
+// Every wave leaves "one of my lanes staged a differing tap" in its own flag BEFORE the forward transform; after it (the
+// transform ends with a barrier) the four flags answer for the whole block.  No barrier of its own.
+__device__ __forceinline__ void stft_note_diff(int* wave_diff, bool diff) {
+    const int any = __any(diff ? 1 : 0);
+    if ((threadIdx.x & 63) == 0) wave_diff[threadIdx.x >> 6] = any;
+}
+__device__ __forceinline__ bool stft_same_frame(const int* wave_diff) {
+    return (wave_diff[0] | wave_diff[1] | wave_diff[2] | wave_diff[3]) == 0;
 }
 
 // ---------------------------------------------------------------- multi-resolution STFT loss
@@ -852,19 +878,25 @@ __global__ __launch_bounds__(256) void stft_loss_fwd_kernel(const float* __restr
     const int f = blockIdx.x, b = blockIdx.y;
     const float* xb = x + (size_t)b * L;
     const float* yb = y + (size_t)b * L;
-    stft_stage_frame<NI, false>(sa, stw, xb, yb, win, tw, f, hop, n, L);
+    __shared__ int wave_diff[4];
+    stft_note_diff(wave_diff, stft_stage_frame<NI, false>(sa, stw, xb, yb, win, tw, f, hop, n, L));
     const cpx* Z = fft_lds_ni<NI, false>(sa, sb, n, logn, stw);
+    const bool same = stft_same_frame(wave_diff);
     float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    for (int k = threadIdx.x; k <= n / 2; k += 256) {
-        cpx X, Y;
-        split_pair(Z, k, n, X, Y);
-        const float xm = sqrtf(fmaxf(X.x * X.x + X.y * X.y, 1e-7f));   // stft_loss.py:30
-        const float ym = sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
-        const float d = ym - xm;
-        s1 = fmaf(d, d, s1);
-        s2 = fmaf(ym, ym, s2);
-        s3 += fabsf(logf(ym) - logf(xm));
-    }
+    // two copies of the loop behind a block-uniform branch: the one every differing frame takes is the code it always was
+    auto bins = [&](auto same_frame) {
+        for (int k = threadIdx.x; k <= n / 2; k += 256) {
+            cpx X, Y;
+            split_pair(Z, k, n, X, Y);
+            const float xm = sqrtf(fmaxf(X.x * X.x + X.y * X.y, 1e-7f));   // stft_loss.py:30
+            const float ym = decltype(same_frame)::value ? xm : sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
+            const float d = ym - xm;
+            s1 = fmaf(d, d, s1);
+            s2 = fmaf(ym, ym, s2);
+            s3 += fabsf(logf(ym) - logf(xm));
+        }
+    };
+    if (same) bins(SameFrame<true>{}); else bins(SameFrame<false>{});
     // three sums of <= 1025 terms: wave shuffles, then the four waves through LDS in fp64 (one barrier instead of the ~30
     // of three tree reductions: they cost more than the FFT itself)
     s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
@@ -900,37 +932,42 @@ __global__ __launch_bounds__(256) void stft_loss_fwdgrad_kernel(const float* __r
     const int f = blockIdx.x, b = blockIdx.y;
     const float* xb = x + (size_t)b * L;
     const float* yb = y + (size_t)b * L;
-    stft_stage_frame<NI, false>(sa, stw, xb, yb, win, tw, f, hop, n, L);
+    __shared__ int wave_diff[4];
+    stft_note_diff(wave_diff, stft_stage_frame<NI, false>(sa, stw, xb, yb, win, tw, f, hop, n, L));
     cpx* Z = fft_lds_ni<NI, false>(sa, sb, n, logn, stw);
+    const bool same = stft_same_frame(wave_diff);
     cpx* other = (Z == sa) ? sb : sa;
     float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    for (int k = threadIdx.x; k <= n / 2; k += 256) {
-        cpx X, Y;
-        split_pair(Z, k, n, X, Y);
-        const float px = X.x * X.x + X.y * X.y;
-        const float xm = sqrtf(fmaxf(px, 1e-7f));   // stft_loss.py:30
-        const float ym = sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
-        const float d = ym - xm;
-        s1 = fmaf(d, d, s1);
-        s2 = fmaf(ym, ym, s2);
-        const float dl = logf(xm) - logf(ym);
-        s3 += fabsf(-dl);
-        cpx Gs = make_float2(0.f, 0.f), Gm = Gs;
-        if (px > 1e-7f) {       // clamp(min=1e-7) passes no gradient below the floor
-            const float sg = (dl > 0.f) ? 1.f : ((dl < 0.f) ? -1.f : 0.f);
-            const float gs = xm - ym, gm = sg / xm;
-            Gs = make_float2(gs * X.x / xm, gs * X.y / xm);
-            Gm = make_float2(gm * X.x / xm, gm * X.y / xm);
+    auto bins = [&](auto same_frame) {
+        for (int k = threadIdx.x; k <= n / 2; k += 256) {
+            cpx X, Y;
+            split_pair(Z, k, n, X, Y);
+            const float px = X.x * X.x + X.y * X.y;
+            const float xm = sqrtf(fmaxf(px, 1e-7f));   // stft_loss.py:30
+            const float ym = decltype(same_frame)::value ? xm : sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
+            const float d = ym - xm;
+            s1 = fmaf(d, d, s1);
+            s2 = fmaf(ym, ym, s2);
+            const float dl = logf(xm) - logf(ym);
+            s3 += fabsf(-dl);
+            cpx Gs = make_float2(0.f, 0.f), Gm = Gs;
+            if (px > 1e-7f) {       // clamp(min=1e-7) passes no gradient below the floor
+                const float sg = (dl > 0.f) ? 1.f : ((dl < 0.f) ? -1.f : 0.f);
+                const float gs = xm - ym, gm = sg / xm;
+                Gs = make_float2(gs * X.x / xm, gs * X.y / xm);
+                Gm = make_float2(gm * X.x / xm, gm * X.y / xm);
+            }
+            // a[i] = Re sum_{k <= n/2} Gs[k] w^{ki} as the inverse transform of its Hermitian extension A (A[k] = Gs[k] / 2,
+            // A[n-k] = conj(Gs[k]) / 2, A[0] = Re Gs[0], A[n/2] = Re Gs[n/2]); the same for Gm -> B; Z' = A + j B
+            if (k == 0 || k == n / 2) {
+                other[k] = make_float2(Gs.x, Gm.x);
+            } else {
+                other[k] = make_float2(0.5f * (Gs.x - Gm.y), 0.5f * (Gs.y + Gm.x));
+                other[n - k] = make_float2(0.5f * (Gs.x + Gm.y), 0.5f * (-Gs.y + Gm.x));
+            }
         }
-        // a[i] = Re sum_{k <= n/2} Gs[k] w^{ki} as the inverse transform of its Hermitian extension A (A[k] = Gs[k] / 2,
-        // A[n-k] = conj(Gs[k]) / 2, A[0] = Re Gs[0], A[n/2] = Re Gs[n/2]); the same for Gm -> B; Z' = A + j B
-        if (k == 0 || k == n / 2) {
-            other[k] = make_float2(Gs.x, Gm.x);
-        } else {
-            other[k] = make_float2(0.5f * (Gs.x - Gm.y), 0.5f * (Gs.y + Gm.x));
-            other[n - k] = make_float2(0.5f * (Gs.x + Gm.y), 0.5f * (-Gs.y + Gm.x));
-        }
-    }
+    };
+    if (same) bins(SameFrame<true>{}); else bins(SameFrame<false>{});
     s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[wave * 3 + 0] = (double)s1; red[wave * 3 + 1] = (double)s2; red[wave * 3 + 2] = (double)s3; }
@@ -1002,7 +1039,9 @@ __global__ __launch_bounds__(1024) void loss_finalize_kernel(const LossDesc d, f
         const float r1 = sqrtf(S1), r2 = sqrtf(S2);
         scs += (double)(r1 / r2);
         mgs += (double)(S3 / (float)d.count[i]);
-        vals[5 + 2 * i] = d.stft_lambda * d.sc_lambda / (float)d.nres / (r1 * r2);
+        // S1 == 0 (the prediction equals the target in every bin): sqrt(S1) / sqrt(S2) has gradient 0 there, as torch's norm
+        // does; 1 / (r1 r2) would be inf, and inf times the exactly-zero gathered frames NaN in every sample
+        vals[5 + 2 * i] = (S1 > 0.f) ? d.stft_lambda * d.sc_lambda / (float)d.nres / (r1 * r2) : 0.f;
         vals[6 + 2 * i] = d.stft_lambda * d.mag_lambda / (float)d.nres / (float)d.count[i];
     }
     const float nres = d.nres > 0 ? (float)d.nres : 1.f;
@@ -1010,6 +1049,7 @@ __global__ __launch_bounds__(1024) void loss_finalize_kernel(const LossDesc d, f
     const float loss = (float)l1 + (sc_l + mg_l);
     loss_out[0] = loss;
     vals[0] = loss; vals[1] = (float)l1; vals[2] = sc_l; vals[3] = mg_l; vals[4] = (float)(1.0 / d.l1_count);
+    for (int i = 0; i < (int)gridDim.x; ++i) scratch[i] = 0.0;       // the contract: the scratch is left all zero
     *counter = 0u;
 }
 
@@ -1071,15 +1111,21 @@ __global__ __launch_bounds__(256) void stft_mag_kernel(const float* __restrict__
     const int f = blockIdx.x, b = blockIdx.y;
     const float* xb = x + (size_t)b * L;
     const float* yb = y + (size_t)b * L;
-    stft_stage_frame<NI, false>(sa, stw, xb, yb, win, tw, f, hop, n, L);
+    __shared__ int wave_diff[4];
+    stft_note_diff(wave_diff, stft_stage_frame<NI, false>(sa, stw, xb, yb, win, tw, f, hop, n, L));
     const cpx* Z = fft_lds_ni<NI, false>(sa, sb, n, logn, stw);
+    const bool same = stft_same_frame(wave_diff);
     const size_t base = ((size_t)b * nframes + f) * (n / 2 + 1);
-    for (int k = threadIdx.x; k <= n / 2; k += 256) {
-        cpx X, Y;
-        split_pair(Z, k, n, X, Y);
-        xmag[base + k] = sqrtf(fmaxf(X.x * X.x + X.y * X.y, 1e-7f));
-        if (ymag) ymag[base + k] = sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
-    }
+    auto bins = [&](auto same_frame) {
+        for (int k = threadIdx.x; k <= n / 2; k += 256) {
+            cpx X, Y;
+            split_pair(Z, k, n, X, Y);
+            const float xm = sqrtf(fmaxf(X.x * X.x + X.y * X.y, 1e-7f));
+            xmag[base + k] = xm;
+            if (ymag) ymag[base + k] = decltype(same_frame)::value ? xm : sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
+        }
+    };
+    if (same) bins(SameFrame<true>{}); else bins(SameFrame<false>{});
 }
 
 // out[c] = sum_g partials[g*ncols + c], one block of 1024 threads per column, four loads in flight per thread, fp64
@@ -1128,34 +1174,40 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(const float* __restrict__
     const int f = blockIdx.x, b = blockIdx.y;
     const float* xb = x + (size_t)b * L;
     const float* yb = MAG ? xb : y + (size_t)b * L;
-    stft_stage_frame<NI, MAG>(sa, stw, xb, yb, win, tw, f, hop, n, L);
+    __shared__ int wave_diff[4];
+    const bool diff = stft_stage_frame<NI, MAG>(sa, stw, xb, yb, win, tw, f, hop, n, L);
+    if (!MAG) stft_note_diff(wave_diff, diff);
     cpx* Z = fft_lds_ni<NI, false>(sa, sb, n, logn, stw);
+    const bool same = MAG ? false : stft_same_frame(wave_diff);
     cpx* other = (Z == sa) ? sb : sa;
     const float c_sc = MAG ? 0.f : coef[0], c_mag = MAG ? 0.f : coef[1];
     const float* gm_row = MAG ? gmag + ((size_t)b * gridDim.x + f) * (n / 2 + 1) : nullptr;
     // build the half spectrum of gradients in `other` (upper half zero), then inverse FFT, real part
-    for (int k = threadIdx.x; k < n; k += 256) {
-        cpx G = make_float2(0.f, 0.f);
-        if (k <= n / 2) {
-            cpx X, Y;
-            split_pair(Z, k, n, X, Y);
-            const float px = X.x * X.x + X.y * X.y;
-            if (px > 1e-7f) {   // clamp(min=1e-7) passes no gradient below the floor
-                const float xm = sqrtf(px);
-                float gm;
-                if (MAG) {
-                    gm = gm_row[k];
-                } else {
-                    const float ym = sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
-                    const float dl = logf(xm) - logf(ym);
-                    const float sg = (dl > 0.f) ? 1.f : ((dl < 0.f) ? -1.f : 0.f);
-                    gm = c_sc * (xm - ym) + c_mag * sg / xm;
+    auto bins = [&](auto same_frame) {
+        for (int k = threadIdx.x; k < n; k += 256) {
+            cpx G = make_float2(0.f, 0.f);
+            if (k <= n / 2) {
+                cpx X, Y;
+                split_pair(Z, k, n, X, Y);
+                const float px = X.x * X.x + X.y * X.y;
+                if (px > 1e-7f) {   // clamp(min=1e-7) passes no gradient below the floor
+                    const float xm = sqrtf(px);
+                    float gm;
+                    if (MAG) {
+                        gm = gm_row[k];
+                    } else {
+                        const float ym = decltype(same_frame)::value ? xm : sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, 1e-7f));
+                        const float dl = logf(xm) - logf(ym);
+                        const float sg = (dl > 0.f) ? 1.f : ((dl < 0.f) ? -1.f : 0.f);
+                        gm = c_sc * (xm - ym) + c_mag * sg / xm;
+                    }
+                    G = make_float2(gm * X.x / xm, gm * X.y / xm);
                 }
-                G = make_float2(gm * X.x / xm, gm * X.y / xm);
             }
+            other[k] = G;
         }
-        other[k] = G;
-    }
+    };
+    if (same) bins(SameFrame<true>{}); else bins(SameFrame<false>{});
     const cpx* g = fft_lds_ni<NI, true>(other, Z, n, logn, stw);
     float* fo = fr + ((size_t)b * gridDim.x + f) * wl;
     for (int i = threadIdx.x; i < wl; i += 256) fo[i] = win[left + i] * g[left + i].x;
@@ -1461,12 +1513,22 @@ extern "C" int trunet_reduce_cols(const float* partials, int nparts, int ncols, 
     return trunet_launch_status();
 }
 
-static int ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return ((1 << l) == n) ? l : -1; }
+// The STFT sizes the loss kernels take: powers of two from 8 to STFT_MAX_N.  (2 n + n / 2) complex values of dynamic LDS is
+// 40 KB at n = 2048, inside the 64 KB a kernel gets without raising its limit; n = 4096 would need 80 KB, which no launch
+// here asks for, so the host refuses it instead of accepting a size whose launch fails.
+constexpr int STFT_MAX_N = 2048;
+// log2 n for a power of two in [1, STFT_MAX_N], -1 for anything else (any int: nothing is shifted past the maximum)
+static int ilog2(int n) {
+    if (n < 1 || n > STFT_MAX_N) return -1;
+    int l = 0;
+    while ((1 << l) < n) ++l;
+    return ((1 << l) == n) ? l : -1;
+}
 
 extern "C" int trunet_stft_loss_fwd(const float* x, const float* y, const float* win, const float* tw, float* partials,
                                     int B, int L, int n, int hop, void* stream) {
     const int logn = ilog2(n);
-    if (!x || !y || !win || !tw || !partials || B <= 0 || logn < 3 || n > 4096 || hop <= 0 || L <= n / 2) return TRUNET_EINVAL;
+    if (!x || !y || !win || !tw || !partials || B <= 0 || logn < 3 || hop <= 0 || L <= n / 2) return TRUNET_EINVAL;
     const int nframes = 1 + L / hop;
 #define FWD_(NI_) hipLaunchKernelGGL(stft_loss_fwd_kernel<NI_>, dim3(nframes, B), dim3(256), (2 * n + n / 2) * sizeof(cpx), ST, x, y, \
                                     win, (const cpx*)tw, partials, L, n, logn, hop, nframes)
@@ -1478,7 +1540,7 @@ extern "C" int trunet_stft_loss_fwd(const float* x, const float* y, const float*
 extern "C" int trunet_stft_mag(const float* x, const float* y, const float* win, const float* tw, float* xmag, float* ymag,
                                int B, int L, int n, int hop, void* stream) {
     const int logn = ilog2(n);
-    if (!x || !win || !tw || !xmag || B <= 0 || logn < 3 || n > 4096 || hop <= 0 || L <= n / 2) return TRUNET_EINVAL;
+    if (!x || !win || !tw || !xmag || B <= 0 || logn < 3 || hop <= 0 || L <= n / 2) return TRUNET_EINVAL;
     const int nframes = 1 + L / hop;
 #define MAG_(NI_) hipLaunchKernelGGL(stft_mag_kernel<NI_>, dim3(nframes, B), dim3(256), (2 * n + n / 2) * sizeof(cpx), ST, x, y ? y : x, \
                                     win, (const cpx*)tw, xmag, y ? ymag : nullptr, L, n, logn, hop, nframes)
@@ -1491,7 +1553,7 @@ extern "C" int trunet_stft_loss_bwd_gather(const float* x, const float* y, const
                                            const float* coef, float* frames, float* gx, int B, int L, int n, int hop,
                                            int win_length, void* stream) {
     const int logn = ilog2(n);
-    if (!x || !y || !win || !tw || !coef || !frames || !gx || B <= 0 || logn < 3 || n > 4096 || hop <= 0 || L <= n / 2 ||
+    if (!x || !y || !win || !tw || !coef || !frames || !gx || B <= 0 || logn < 3 || hop <= 0 || L <= n / 2 ||
         win_length <= 0 || win_length > n)
         return TRUNET_EINVAL;
     const int nframes = 1 + L / hop;
@@ -1585,7 +1647,7 @@ extern "C" int trunet_stream_feed_ola(const float* frames, float* ola, float* ou
 extern "C" int trunet_stft_loss_fwdgrad(const float* x, const float* y, const float* win, const float* tw, float* partials,
                                         float* fr_sc, float* fr_mag, int B, int L, int n, int hop, int win_length, void* stream) {
     const int logn = ilog2(n);
-    if (!x || !y || !win || !tw || !partials || !fr_sc || !fr_mag || B <= 0 || logn < 3 || n > 4096 || hop <= 0 || L <= n / 2 ||
+    if (!x || !y || !win || !tw || !partials || !fr_sc || !fr_mag || B <= 0 || logn < 3 || hop <= 0 || L <= n / 2 ||
         win_length <= 0 || win_length > n)
         return TRUNET_EINVAL;
     const int nframes = 1 + L / hop;
@@ -1600,14 +1662,14 @@ extern "C" int trunet_stft_loss_fwdgrad(const float* x, const float* y, const fl
 extern "C" size_t trunet_loss_scratch_bytes(void) { return (1 + 3 * TRUNET_MAX_RES + 1) * sizeof(double); }
 
 extern "C" int trunet_loss_finalize(const trunet_loss_args* a, float* loss_out, float* vals, void* scratch, void* stream) {
-    if (!a || !loss_out || !vals || !scratch || !a->l1_partials || a->n_l1 <= 0 || a->l1_count <= 0 || a->nres < 0 ||
+    if (!a || !loss_out || !vals || !scratch || !a->l1_partials || a->n_l1 <= 0 || !(a->l1_count > 0) || a->nres < 0 ||
         a->nres > TRUNET_MAX_RES)
         return TRUNET_EINVAL;
     LossDesc d;
     d.l1_partials = a->l1_partials; d.n_l1 = a->n_l1; d.nres = a->nres; d.l1_count = a->l1_count;
     d.sc_lambda = a->sc_lambda; d.mag_lambda = a->mag_lambda; d.stft_lambda = a->stft_lambda;
     for (int i = 0; i < a->nres; ++i) {
-        if (!a->parts[i] || a->nrows[i] <= 0 || a->count[i] <= 0) return TRUNET_EINVAL;
+        if (!a->parts[i] || a->nrows[i] <= 0 || !(a->count[i] > 0)) return TRUNET_EINVAL;
         d.parts[i] = a->parts[i]; d.nrows[i] = a->nrows[i]; d.count[i] = a->count[i];
     }
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1 + 3 * a->nres), dim3(1024), 0, ST, d, loss_out, vals, (double*)scratch);
@@ -1635,7 +1697,7 @@ extern "C" int trunet_loss_grad_gather(const trunet_loss_gather_args* a, const f
 extern "C" int trunet_stft_mag_bwd(const float* x, const float* win, const float* tw, const float* gmag, float* frames,
                                    float* gx, int B, int L, int n, int hop, int win_length, void* stream) {
     const int logn = ilog2(n);
-    if (!x || !win || !tw || !gmag || !frames || !gx || B <= 0 || logn < 3 || n > 4096 || hop <= 0 || L <= n / 2 ||
+    if (!x || !win || !tw || !gmag || !frames || !gx || B <= 0 || logn < 3 || hop <= 0 || L <= n / 2 ||
         win_length <= 0 || win_length > n)
         return TRUNET_EINVAL;
     const int nframes = 1 + L / hop;

@@ -85,7 +85,10 @@ class _STFTLossFn(torch.autograd.Function):
     def backward(ctx, g_sc, g_mag):
         x, y, win, tw, sums = ctx.saved_tensors
         B, Ln = x.shape
-        coef = torch.stack([g_sc / (torch.sqrt(sums[0]) * torch.sqrt(sums[1])), g_mag / ctx.count]).float().contiguous()
+        # S1 == 0 (x equals y in every bin): the gradient of sqrt(S1) / sqrt(S2) is 0 there, as torch's norm has it; the
+        # quotient would be inf, and inf * (xm - ym) = inf * 0 NaN in every bin
+        c_sc = torch.where(sums[0] > 0, g_sc / (torch.sqrt(sums[0]) * torch.sqrt(sums[1])), torch.zeros_like(g_sc))
+        coef = torch.stack([c_sc, g_mag / ctx.count]).float().contiguous()
         # overlap-add as a gather over the window's support: no float atomics
         nfr = 1 + Ln // ctx.hop
         frames = torch.empty((B, nfr, ctx.wl), device=x.device, dtype=torch.float32)
