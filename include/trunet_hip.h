@@ -608,6 +608,27 @@ int trunet_reverb_mix(const float* clean, const float* noise, const float* rir, 
                       int early_taps, float peak, float* noisy, float* target, void* ws, size_t ws_bytes, int B, int L,
                       int Kmax, void* stream);
 
+/* ---- room simulation: image-source RIRs with a diffuse tail (build extension) ----
+ * rooms is (B, row_floats) on the device, row_floats == 18: Lx Ly Lz | sx sy sz | rx ry rz | bx0 bx1 by0 by1 bz0 bz1 | rt60 |
+ * seed_lo seed_hi (metres, reflection coefficients with x0 the wall at x = 0 and x1 the wall at x = Lx, seconds, the two 16-bit
+ * halves of the seed as exactly representable floats).  Per row, K_b = clamp(round(min(rt60, max_rir_sec) fs), 1, Kmax):
+ *   taps [0, min(n_c, K_b))   image-source method: sum over the images I of  gain 0.5 (1 + cos(2 pi (n - tau) / tw)) sinc(n - tau),
+ *                             |n - tau| < tw / 2, tau = (|I - r| - |s - r|) fs / c, gain = prod beta^order |s - r| / |I - r|:
+ *                             the direct path is exactly a unit tap at n = 0
+ *   taps [n_c, K_b)           sigma_c g(seed, n) exp(-6.9078 (n - n_c + W/2) / (rt60 fs)), W = max(round(0.010 fs), 1),
+ *                             sigma_c^2 the mean square of the W (at most n_c) taps before n_c, g a counter-based standard normal
+ *   taps [K_b, Kmax)          zeros;   rir_len[b] = K_b
+ * A row that is all zero or malformed (NaN, Inf, a dimension below 2 m, source or microphone not strictly inside or closer than
+ * 1 mm to each other, |beta| > 1, rt60 <= 0, seed halves that are not integers in [0, 65535]) gives rir_len[b] = 0 and a zero
+ * row.  Image orders are clamped to 96 per axis, so the work of a call is bounded whatever the rows hold.  Fixed-point
+ * accumulation (2^-40) in LDS, no float atomics: a row's taps repeat bit for bit, alone, in any batch and under any Kmax.
+ * ws: trunet_rir_ism_workspace_bytes(B, Kmax) bytes (0 for arguments out of range), reserved.  TRUNET_EINVAL: NULL rooms / rir /
+ * rir_len / ws, row_floats != 18, B outside [1, 65535], Kmax, n_c or tw < 1, fs, c or max_rir_sec not positive and finite, a
+ * short workspace.  TRUNET_ENOTSUP: Kmax > 65536, n_c > 8192, tw even or above 129, (n_c + tw/2 + 1) c / fs > 360 m. */
+size_t trunet_rir_ism_workspace_bytes(int B, int Kmax);
+int trunet_rir_ism(const float* rooms, int row_floats, float* rir, int32_t* rir_len, int B, int Kmax, float fs, float c,
+                   int n_c, int tw, float max_rir_sec, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- time-domain loss terms: segmental cosine similarity (cos_loss.py:4-56 repaired, R8) and SI-SDR ----
  * x = audio (the estimate), y = clean, both (B, L) fp32.
  * Cosine term: bounds[0 .. nseg] = 0, g[0], g[1], ... each clipped to L gives the nseg segments [bounds[i], bounds[i+1]):

@@ -227,6 +227,8 @@ def _declare(L):
         "trunet_augment_mix": [p, p, p, p, p, i, i, p],
         "trunet_reverb_workspace_bytes": [i, i, i],
         "trunet_reverb_mix": [p, p, p, p, p, i, f, p, p, p, C.c_size_t, i, i, i, p],
+        "trunet_rir_ism_workspace_bytes": [i, i],
+        "trunet_rir_ism": [p, i, p, p, i, i, f, f, i, i, f, p, C.c_size_t, p],
         "trunet_wave_loss_workspace_bytes": [i, i, i],
         "trunet_wave_loss_fwd": [C.POINTER(WaveLossArgs), p, C.c_size_t, p, p, p, p, p],
         "trunet_wave_loss_grad": [C.POINTER(WaveLossArgs), p, p, p, p],
@@ -268,6 +270,7 @@ def _declare(L):
     L.trunet_loss_scratch_bytes.restype = C.c_size_t
     L.trunet_stoi_workspace_bytes.restype = C.c_size_t
     L.trunet_reverb_workspace_bytes.restype = C.c_size_t
+    L.trunet_rir_ism_workspace_bytes.restype = C.c_size_t
     L.trunet_wave_loss_workspace_bytes.restype = C.c_size_t
     L._declared = sorted(sig)
 

@@ -9,7 +9,8 @@
   reference's loader (train.py:121), already resident in HBM (the ``.cuda()`` of train.py:124-125 is then a no-op);
 * an extension for the dereverberation half of TRU-Net: ``Reverb`` and the ``reverb=`` / ``snr_db=`` keywords of the
   dataset and the loader convolve every pair with a room impulse response, mix at a drawn SNR and guard the peak, as one
-  more GPU stage of the loader (``trunet_reverb_mix``, reverb.hip).
+  more GPU stage of the loader (``trunet_reverb_mix``, reverb.hip); ``RoomSim`` simulates the impulse responses on the GPU
+  as well (``trunet_rir_ism``, roomsim.hip: image sources and a diffuse tail), so the stage needs no RIR corpus.
 """
 import math
 import os
@@ -137,6 +138,130 @@ def _read_wav(path):
     return torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)), sr
 
 
+class RoomSim:
+    """Shoebox room simulator (an extension): image-source RIRs up to ``ism_ms`` and a stochastic diffuse
+    tail after it, one room per row, on the GPU (``trunet_rir_ism``, roomsim.hip).  ``draw()`` picks a room, a source and
+    a microphone on the host (Python's ``random``) and returns them as ONE row of ``ROW`` floats; ``__call__`` turns a
+    batch of rows into RIRs whose direct path is a unit tap at 0, the alignment ``Reverb.prepare`` gives measured RIRs.
+    The object holds parameters only (the GPU workspace is dropped on pickling), so it travels to DataLoader workers.
+
+    Row layout: Lx Ly Lz | sx sy sz | rx ry rz | six wall reflection coefficients x0 x1 y0 y1 z0 z1 | rt60 | seed_lo seed_hi."""
+
+    ROW = 18
+    MAX_ISM_TAPS, MAX_TW, MAX_TAPS, MAX_ORDER, MAX_SPAN_M, MIN_DIM = 8192, 129, 65536, 96, 360.0, 2.0
+
+    def __init__(self, sample_rate=16000, room_dim=((3, 10), (3, 8), (2.4, 4)), rt60=(0.2, 1.0), wall_margin=0.5,
+                 distance=(0.3, 3.0), ism_ms=80.0, max_rir_sec=1.0, tw=81, c=343.0):
+        self.sample_rate = int(sample_rate)
+        self.room_dim = tuple((float(lo), float(hi)) for lo, hi in room_dim)
+        self.rt60 = (float(rt60[0]), float(rt60[1]))
+        self.wall_margin = float(wall_margin)
+        self.distance = (float(distance[0]), float(distance[1]))
+        self.ism_ms, self.max_rir_sec, self.tw, self.c = float(ism_ms), float(max_rir_sec), int(tw), float(c)
+        if self.sample_rate <= 0 or not self.c > 0 or not self.max_rir_sec > 0:
+            raise ValueError("RoomSim: sample_rate, c and max_rir_sec must be positive")
+        if len(self.room_dim) != 3 or any(not (self.MIN_DIM <= lo <= hi < float("inf")) for lo, hi in self.room_dim):
+            raise ValueError("RoomSim: room_dim is three (lo, hi) ranges in metres with lo >= %g" % self.MIN_DIM)
+        if not 0 < self.rt60[0] <= self.rt60[1] < float("inf"):
+            raise ValueError("RoomSim: rt60 is a (lo, hi) range of positive seconds")
+        inner = [lo - 2 * self.wall_margin for lo, _ in self.room_dim]
+        if self.wall_margin < 0 or min(inner) <= 0:
+            raise ValueError("RoomSim: wall_margin leaves no space in the smallest room")
+        if not 1e-3 < self.distance[0] <= self.distance[1] or self.distance[0] >= math.sqrt(sum(v * v for v in inner)):
+            raise ValueError("RoomSim: the distance range does not fit the smallest room")
+        if self.tw < 1 or self.tw % 2 == 0 or self.tw > self.MAX_TW:
+            raise ValueError("RoomSim: tw must be odd and at most %d" % self.MAX_TW)
+        if not 1 <= self.n_c <= self.MAX_ISM_TAPS:
+            raise ValueError("RoomSim: ism_ms * sample_rate = %d taps, outside [1, %d]" % (self.n_c, self.MAX_ISM_TAPS))
+        if not 1 <= self.max_taps <= self.MAX_TAPS:
+            raise ValueError("RoomSim: RIRs of %d taps are out of range (at most %d)" % (self.max_taps, self.MAX_TAPS))
+        span = (self.n_c + self.tw // 2 + 1) * self.c / self.sample_rate
+        diag = math.sqrt(sum(hi * hi for _, hi in self.room_dim))
+        if span > self.MAX_SPAN_M or 1 + (diag + span) / (2 * min(lo for lo, _ in self.room_dim)) > self.MAX_ORDER:
+            raise ValueError("RoomSim: images %.0f m away exceed the kernel's caps (%g m, order %d per axis)"
+                             % (span, self.MAX_SPAN_M, self.MAX_ORDER))
+        self._ws = {}
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_ws"] = {}
+        return d
+
+    @property
+    def n_c(self):
+        """the crossover tap: image sources before it, the diffuse tail from it on"""
+        return int(round(self.ism_ms * self.sample_rate / 1000.0))
+
+    @property
+    def max_taps(self):
+        return int(round(self.max_rir_sec * self.sample_rate))
+
+    @staticmethod
+    def sabine(dim, rt60):
+        """one reflection coefficient for all six walls from Sabine's formula: alpha = min(0.161 V / (S rt60), 0.99)"""
+        lx, ly, lz = (float(v) for v in dim)
+        alpha = min(0.161 * lx * ly * lz / (2.0 * (lx * ly + ly * lz + lx * lz) * float(rt60)), 0.99)
+        return math.sqrt(1.0 - alpha)
+
+    @classmethod
+    def row(cls, dim, src, mic, beta, rt60, seed):
+        """a row from explicit values; ``beta`` is one coefficient or six (x0, x1, y0, y1, z0, z1), ``seed`` in [0, 2^32)"""
+        beta = [float(beta)] * 6 if np.ndim(beta) == 0 else [float(v) for v in beta]
+        seed = int(seed)
+        if len(beta) != 6 or len(dim) != 3 or len(src) != 3 or len(mic) != 3 or not 0 <= seed < 2 ** 32:
+            raise ValueError("RoomSim.row: three dimensions, two points, one or six coefficients, a 32-bit seed")
+        vals = [float(v) for v in dim] + [float(v) for v in src] + [float(v) for v in mic] + beta
+        return torch.tensor(vals + [float(rt60), float(seed & 0xFFFF), float(seed >> 16)], dtype=torch.float32)
+
+    @classmethod
+    def fields(cls, row):
+        """the arguments of ``row()`` back from a row (float32 values as Python numbers)"""
+        v = [float(x) for x in torch.as_tensor(row).reshape(cls.ROW)]
+        return {"dim": tuple(v[0:3]), "src": tuple(v[3:6]), "mic": tuple(v[6:9]), "beta": tuple(v[9:15]), "rt60": v[15],
+                "seed": int(v[16]) | (int(v[17]) << 16)}
+
+    def draw(self):
+        """one random room as a row: dimensions and rt60 uniform in their ranges, Sabine's coefficient on all six walls,
+        source and microphone redrawn until both keep wall_margin from every wall and their distance lies in ``distance``"""
+        f32 = lambda x: float(np.float32(x))                   # the row is float32: test what the kernel will see
+        dim = [f32(random.uniform(lo, hi)) for lo, hi in self.room_dim]
+        rt60 = random.uniform(*self.rt60)
+        m = self.wall_margin
+        while True:
+            src = [f32(random.uniform(m, v - m)) for v in dim]
+            mic = [f32(random.uniform(m, v - m)) for v in dim]
+            inside = all(m <= p <= v - m for pt in (src, mic) for p, v in zip(pt, dim))
+            if inside and self.distance[0] <= math.dist(src, mic) <= self.distance[1]:
+                break
+        return self.row(dim, src, mic, self.sabine(dim, rt60), rt60, random.randrange(2 ** 32))
+
+    def __call__(self, rows):
+        """rows: (B, ROW) on the GPU -> (rir (B, Kmax) fp32, lens (B,) int32), Kmax = round(max_rir_sec * sample_rate); a
+        row of zeros (the collate's padding for "no room") gives length 0 and a zero RIR.  Asynchronous on the current
+        stream; the workspace is kept per stream and reused."""
+        _need_gpu(rows)
+        dev = rows.device
+        rows = rows.contiguous().float()
+        if rows.dim() != 2 or rows.shape[1] != self.ROW:
+            raise ValueError("RoomSim expects (B, %d) rows, got %s" % (self.ROW, tuple(rows.shape)))
+        B, Kmax = rows.shape[0], self.max_taps
+        rir = torch.empty((B, Kmax), device=dev, dtype=torch.float32)
+        lens = torch.empty((B,), device=dev, dtype=torch.int32)
+        if B == 0:
+            return rir, lens
+        ws_bytes = int(L.lib().trunet_rir_ism_workspace_bytes(B, Kmax))
+        if ws_bytes == 0:
+            raise L.TrunetHipError("trunet_rir_ism: %d rows of %d taps are out of range" % (B, Kmax))
+        key = (str(dev), L.stream())
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < ws_bytes:
+            ws = self._ws[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(L.lib().trunet_rir_ism(ptr(rows), self.ROW, ptr(rir), lens.data_ptr(), B, Kmax, float(self.sample_rate),
+                                     self.c, self.n_c, self.tw, self.max_rir_sec, ws.data_ptr(), ws_bytes, L.stream()),
+              "rir_ism")
+        return rir, lens
+
+
 class Reverb:
     """Room simulation for the training pairs (an extension: the reference has gain and biquads only).
     ``draw()`` picks a room impulse response per item on the host (Python's ``random``, like ``DataAugment.draw``);
@@ -147,14 +272,28 @@ class Reverb:
 
     with ``h[0]`` the direct path, so the target stays time-aligned with ``noisy``.  RIRs come from the wav files of
     ``rir_root`` (mono or channel 0, at ``sample_rate`` exactly: there is no resampling) or, without a folder, from
-    ``synthetic()``: exponentially decaying Gaussian noise with the drawn RT60 and direct-to-reverberant ratio."""
+    ``synthetic()``: exponentially decaying Gaussian noise with the drawn RT60 and direct-to-reverberant ratio.
+
+    With ``room`` (a ``RoomSim``) the RIRs are simulated on the GPU instead: ``draw()`` returns the room's parameter row in
+    place of taps, the collate pads and batches the rows like taps, and ``__call__`` reads a ``(B, RoomSim.ROW)`` tensor as
+    rows: it runs the simulator on them, then the same convolution stage on the result."""
 
     PEAK = 0.99
 
     def __init__(self, rir_root=None, sample_rate=16000, p_reverb=0.5, rt60=(0.2, 1.0), drr_db=(0.0, 15.0),
-                 max_rir_sec=1.0, target="dry", early_ms=50.0):
+                 max_rir_sec=1.0, target="dry", early_ms=50.0, room=None):
         if target not in ("dry", "early"):
             raise ValueError("Reverb target must be 'dry' or 'early', got %r" % (target,))
+        if room is not None:
+            if rir_root is not None:
+                raise ValueError("Reverb takes its RIRs from rir_root or from room, not both")
+            if room.sample_rate != int(sample_rate):
+                raise ValueError("RoomSim is built for %d Hz, Reverb for %d Hz (no resampling)"
+                                 % (room.sample_rate, int(sample_rate)))
+            if target == "early" and float(early_ms) > room.ism_ms:
+                raise ValueError("the early target (%g ms) must lie in the image-source part of the RIR (ism_ms = %g)"
+                                 % (float(early_ms), room.ism_ms))
+        self.room = room
         self.rir_root, self.sample_rate, self.p_reverb = rir_root, int(sample_rate), float(p_reverb)
         self.rt60, self.drr_db, self.max_rir_sec = tuple(rt60), tuple(drr_db), float(max_rir_sec)
         self.target, self.early_ms = target, float(early_ms)
@@ -202,9 +341,12 @@ class Reverb:
         return torch.from_numpy(np.ascontiguousarray(h, dtype=np.float32))
 
     def draw(self):
-        """a 1-D float32 RIR, or an empty tensor (no reverberation) with probability 1 - p_reverb"""
+        """a 1-D float32 RIR (with ``room``: its parameter row), or an empty tensor (no reverberation) with probability
+        1 - p_reverb"""
         if random.random() >= self.p_reverb:
             return torch.empty(0, dtype=torch.float32)
+        if self.room is not None:                           # the room's parameter row: the taps are made on the GPU
+            return self.room.draw()
         if self.files is not None:
             path = os.path.join(self.rir_root, random.choice(self.files))
             h, sr = _read_wav(path)
@@ -220,6 +362,8 @@ class Reverb:
     def __call__(self, clean, rirs, lens, noise=None, snr_db=None):
         """clean, noise: (B, 1, L) on the GPU (noise already augmented, or None); rirs: (B, Kmax) zero-padded, lens: (B,)
         int32 tap counts (0 = the row does not reverberate); snr_db: (B,) or None (unit gain) -> (noisy, target).
+        With ``room``, rirs of shape (B, RoomSim.ROW) are parameter rows (all zero: no room): their RIRs and tap counts come
+        from the simulator, on the same stream, and ``lens`` is not read.
         Asynchronous on the current stream; the workspace is kept per stream and reused."""
         _need_gpu(clean)
         dev = clean.device
@@ -230,6 +374,10 @@ class Reverb:
         noise = None if noise is None else noise.to(dev).contiguous().float()
         if noise is not None and noise.numel() != clean.numel():
             raise ValueError("noise must have the shape of clean")
+        if self.room is not None and rirs is not None and rirs.dim() == 2 and rirs.shape[-1] == RoomSim.ROW:
+            if rirs.shape[0] != B:
+                raise ValueError("one room row per signal")
+            rirs, lens = self.room(rirs.to(dev))
         Kmax = 0 if rirs is None else int(rirs.shape[-1])
         rirs_d = lens_d = ws = None
         ws_bytes = 0
