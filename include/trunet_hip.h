@@ -477,6 +477,19 @@ int trunet_mask_istft_ragged(const float* net_out, float* frames, float* audio, 
  *   chunk. */
 int trunet_resample_ragged(const float* in, float* out, const int64_t* in_off, const int64_t* out_off, const float* taps,
                            int half, int p, int q, int B, int64_t total_in, int64_t total_out, int nsig, void* stream);
+/* trunet_resample_rational (resample.py): the same definition and the same in_off / out_off tables for any
+ * ratio with p, q <= 640, total_in and total_out below 2^31.  A workgroup stages the input span of one tile of `tile`
+ * consecutive outputs of one utterance (tiles counted from the utterance's first output; tile a multiple of 256, at most
+ * 4096) in LDS; tile_off = int64 DEVICE prefix of ceil(M_b / tile), M_b = ceil(L_b p / q), total_tiles its last entry.
+ * half = zeros * max(p, q) with 1 <= zeros <= 32, K = ceil((2 half + 1) / p); table = the taps phase-major, p rows of
+ * Kp = K rounded up to a multiple of 4 floats, table[r * Kp + k] = taps[r + k p] (zero past the last tap), 16-byte aligned.
+ * taps_in_lds: 1 = every workgroup copies the table into LDS (p * Kp <= 16384), 0 = rows are read from L2.  fp32
+ * accumulation per output with k ascending; results are bit for bit independent of the batch.  TRUNET_EINVAL without a
+ * launch for anything the host can see; an utterance whose device offsets contradict each other is skipped. */
+int trunet_resample_rational(const float* in, float* out, const int64_t* in_off, const int64_t* out_off,
+                             const int64_t* tile_off, const float* table, int half, int K, int p, int q, int tile, int B,
+                             int64_t total_in, int64_t total_out, int64_t total_tiles, int nsig, int taps_in_lds,
+                             void* stream);
 size_t trunet_stoi_workspace_bytes(int B, int64_t total_frames, int64_t total_segments);
 int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, const int64_t* frame_off, const int64_t* seg_off,
                        const int64_t* chunk_off, const float* window, const int* band_edges, const float* tw512,

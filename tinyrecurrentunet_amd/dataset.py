@@ -87,7 +87,9 @@ def _biquad(kind, sr, cutoff, Q=0.7):
 class DataAugment:
     """dataset.py:79-126: gain in [-12, -5) dB, low-pass biquad 7-10 kHz, high-pass biquad 0.8-1.2 kHz (Q = 0.7) on the
     noise signal.  ``draw()`` picks the three parameters with the reference's ``random.choice`` calls in the reference's
-    order; ``__call__`` applies them to a (..., L) tensor on the GPU (one launch for all leading rows)."""
+    order; ``__call__`` applies them to a (..., L) tensor on the GPU (one launch for all leading rows).  The biquads keep
+    their fixed 48 kHz design (``self.sr``), as in the reference, whatever rate the signal has: also after the loader's
+    ``resample_to``."""
 
     def __init__(self):
         self.min_gain, self.max_gain = -12.0, -5.0
@@ -414,15 +416,29 @@ class CleanNoisyPairDataset(Dataset):
 
     ``reverb`` (a ``Reverb``) and ``snr_db`` (a ``(lo, hi)`` range in dB, uniform per item) are extensions; with either set a
     training element carries two more entries, ``(..., rir (K,), snr or None)``, drawn AFTER everything the 4-tuple draws, and
-    the loader runs the reverberation stage.  With both ``None`` nothing changes, random-number consumption included."""
+    the loader runs the reverberation stage.  With both ``None`` nothing changes, random-number consumption included.
 
-    def __init__(self, root="./", subset="training", crop_length_sec=0, sample_rate=48000, *, reverb=None, snr_db=None):
+    ``resample_to`` (an extension): ``sample_rate`` is the rate of the files, as in config/tiny.json, and the workers crop at
+    it exactly as without; the loader then resamples clean and noise to ``resample_to`` on the GPU before it mixes
+    (``resample.Resampler``, both signals in one launch).  A file at another rate than ``sample_rate`` is then an error,
+    and a ``Reverb`` must be built for ``resample_to``.  With ``None`` elements and batches are exactly as before."""
+
+    def __init__(self, root="./", subset="training", crop_length_sec=0, sample_rate=48000, *, reverb=None, snr_db=None,
+                 resample_to=None):
         super().__init__()
         assert subset is None or subset in ["training", "testing"]
         self.root, self.subset = root, subset
-        if reverb is not None and reverb.sample_rate != sample_rate:
+        if resample_to is not None:
+            from .resample import ratio
+            ratio(sample_rate, resample_to)
+            resample_to = int(resample_to)
+            if reverb is not None and reverb.sample_rate != resample_to:
+                raise ValueError("Reverb is built for %d Hz, the dataset resamples to %d Hz"
+                                 % (reverb.sample_rate, resample_to))
+        elif reverb is not None and reverb.sample_rate != sample_rate:
             raise ValueError("Reverb is built for %d Hz, the dataset for %d Hz (no resampling)"
                              % (reverb.sample_rate, sample_rate))
+        self.resample_to = resample_to
         self.reverb = reverb
         self.snr_db = None if snr_db is None else (float(snr_db[0]), float(snr_db[1]))
         self.aug = DataAugment()
@@ -459,9 +475,11 @@ class CleanNoisyPairDataset(Dataset):
         fileid = self.files[n]
         crop_length = int(self.crop_length_sec * self.sample_rate)
         if self.subset == "testing" and not self.synthetic:
-            clean, _ = _read_wav(fileid[0])
-            noisy, _ = _read_wav(fileid[1])
+            clean, sr = _read_wav(fileid[0])
+            noisy, sr2 = _read_wav(fileid[1])
             assert len(clean) == len(noisy)
+            self._check_rate(fileid[0], sr)
+            self._check_rate(fileid[1], sr2)
             # no augmentation: unit gain and identity "filters" are not expressible as biquads, so the loader mixes
             # nothing for testing items (params = None): the second element already IS the noisy signal
             return clean.unsqueeze(0), noisy.unsqueeze(0), fileid, torch.zeros(11)
@@ -472,7 +490,9 @@ class CleanNoisyPairDataset(Dataset):
         else:
             noise_file = random.choice(self.noise_files)
             clean, sr = _read_wav(fileid)
-            noise, _ = _read_wav(os.path.join(self.root, "keyboard", noise_file))
+            noise, sr2 = _read_wav(os.path.join(self.root, "keyboard", noise_file))
+            self._check_rate(fileid, sr)
+            self._check_rate(noise_file, sr2)
             self.sample_rate = sr
             crop_length = int(self.crop_length_sec * sr)
         params = torch.from_numpy(self.aug.params(*self.aug.draw()))
@@ -488,6 +508,12 @@ class CleanNoisyPairDataset(Dataset):
         rir = self.reverb.draw() if self.reverb is not None else torch.empty(0, dtype=torch.float32)
         snr = random.uniform(*self.snr_db) if self.snr_db is not None else None
         return clean.unsqueeze(0), noise.unsqueeze(0), fileid, params, rir, snr
+
+    def _check_rate(self, name, sr):
+        """with resample_to the loader converts from ``sample_rate``: the rate a worker reads cannot reach it otherwise"""
+        if self.resample_to is not None and sr != self.sample_rate:
+            raise ValueError("%s is sampled at %d Hz, the dataset resamples from %d Hz to %d Hz"
+                             % (name, sr, self.sample_rate, self.resample_to))
 
     def __len__(self):
         return len(self.files)
@@ -518,11 +544,25 @@ class GpuPairLoader:
     def __init__(self, loader, mix=True):
         self.loader, self.mix = loader, mix
         self._plain = None                     # the stage without a room, for a dataset with snr_db only
+        self._resampler = None
         self.dataset = loader.dataset
         self.sampler = loader.sampler
 
     def __len__(self):
         return len(self.loader)
+
+    def _resample(self, clean_d, other_d, dev):
+        """dataset.resample_to: clean and noise (B, 1, L) at the files' rate -> (B, 1, ceil(L p / q)), both in one launch
+        on the current (side) stream"""
+        to = getattr(self.dataset, "resample_to", None)
+        if to is None or to == self.dataset.sample_rate:
+            return clean_d, other_d
+        if self._resampler is None or self._resampler.fs_in != self.dataset.sample_rate or self._resampler.device != dev:
+            from .resample import Resampler
+            self._resampler = Resampler(self.dataset.sample_rate, to, dev)
+        B, _, Ln = clean_d.shape
+        y = self._resampler.rows(torch.stack([clean_d.view(B, Ln), other_d.view(B, Ln)]))
+        return y[0].unsqueeze(1), y[1].unsqueeze(1)
 
     def _stage(self, batch, side):
         if batch is None:
@@ -536,6 +576,7 @@ class GpuPairLoader:
         with torch.cuda.stream(side):
             clean_d = clean.to(dev, non_blocking=True).float().contiguous()
             other_d = other.to(dev, non_blocking=True).float().contiguous()
+            clean_d, other_d = self._resample(clean_d, other_d, dev)
             if self.mix:
                 par_d = params.to(dev, non_blocking=True).float().contiguous()
                 B, _, Ln = other_d.shape
@@ -556,10 +597,12 @@ class GpuPairLoader:
             raise L.TrunetHipError("reverb / snr_db apply to training items, which carry a noise signal to mix")
         rv = self.dataset.reverb or self._plain
         if rv is None:
-            rv = self._plain = Reverb(p_reverb=0.0, sample_rate=self.dataset.sample_rate)
+            rv = self._plain = Reverb(p_reverb=0.0, sample_rate=getattr(self.dataset, "resample_to", None) or
+                                      self.dataset.sample_rate)
         with torch.cuda.stream(side):
             clean_d = clean.to(dev, non_blocking=True).float().contiguous()
             other_d = other.to(dev, non_blocking=True).float().contiguous()
+            clean_d, other_d = self._resample(clean_d, other_d, dev)
             par_d = params.to(dev, non_blocking=True).float().contiguous()
             rirs_d = rirs.to(dev, non_blocking=True)
             lens_d = lens.to(dev, non_blocking=True)
@@ -587,13 +630,15 @@ class GpuPairLoader:
 
 
 def load_CleanNoisyPairDataset(root, subset, crop_length_sec, batch_size, sample_rate, num_gpus=1, num_workers=4, *,
-                               reverb=None, snr_db=None):
+                               reverb=None, snr_db=None, resample_to=None):
     """dataset.py:393-412: same arguments (``**trainset_config`` of config/tiny.json + subset, batch_size, num_gpus);
     DistributedSampler when num_gpus > 1, else shuffle.  Returns an iterable of (clean (B,1,L), noisy (B,1,L), fileid).
     ``reverb`` / ``snr_db`` (keyword-only extensions, see ``Reverb``): the training pairs are reverberated and mixed at a
-    drawn SNR on the GPU; the first element is then the dereverberation target the ``Reverb`` was built for."""
+    drawn SNR on the GPU; the first element is then the dereverberation target the ``Reverb`` was built for.
+    ``resample_to`` (keyword-only extension): the files are at ``sample_rate``; clean and noise are resampled to
+    ``resample_to`` on the GPU before the mix, so the batches have ceil(L resample_to / sample_rate) samples."""
     dataset = CleanNoisyPairDataset(root=root, subset=subset, crop_length_sec=crop_length_sec, sample_rate=sample_rate,
-                                    reverb=reverb, snr_db=snr_db)
+                                    reverb=reverb, snr_db=snr_db, resample_to=resample_to)
     kwargs = {"batch_size": batch_size, "num_workers": num_workers, "pin_memory": torch.cuda.is_available(),
               "drop_last": False, "collate_fn": _collate_pairs}
     if num_gpus > 1:

@@ -6,7 +6,8 @@ tensor with ``lengths`` and returns the denoised audio with exactly each input's
 offline path of ``util.loss_fn`` -- centred rect STFT with reflect padding and PCEN from the utterance's first frame
 (``dataset.py:56-76,246-272``), the network in eval mode, phase-aware mask and ``torch.istft(..., length=L)``
 (``phm.py:31-45``, ``dataset.py:293-296``) -- and does not depend on which other utterances share the call, their order,
-or the chunking of the frames.  A call is
+or the chunking of the frames.  Audio at another rate (``fs=``, 8 to 96 kHz) is resampled to 16 kHz and back on the GPU
+around the same call (resample.py).  A call is
 
     pack          the utterances back to back + their offset tables (one host -> device copy)
     features      trunet_stft_features_ragged (+ trunet_pcen_ragged for C_in = 4): one launch each for the whole batch
@@ -23,7 +24,7 @@ other layer acts per frame with eval BatchNorm.
 
 Command line (the ``denoise.py`` role)::
 
-    python -m tinyrecurrentunet_amd.enhance --checkpoint CKPT --input-size {3,4} [--use-tgru] --in DIR --out DIR
+    python -m tinyrecurrentunet_amd.enhance --checkpoint CKPT --input-size {3,4} [--use-tgru] --in DIR --out DIR [--resample]
 """
 import argparse
 import math
@@ -99,7 +100,7 @@ def _inputs(x, lengths):
 
 
 @torch.no_grad()
-def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
+def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAMPLE_RATE):
     """Denoise recordings of any lengths with ``net`` (a ``network.TRUNet`` in eval mode, on the GPU).
 
     x: a list of 1-D fp32 cuda tensors -> list of 1-D tensors of the same lengths; or a (B, Lmax) tensor with ``lengths``
@@ -108,7 +109,10 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
     a single longer utterance being a group of its own).  path: "folded" (the single-launch eval artefact, fp32), "layers"
     (the layer kernels in the net's precision) or "auto" (folded unless ``net.fold_eval`` is off; a ``use_tgru`` net
     always runs the layer kernels, the only ones that carry the block over whole sequences); "int8" quantizes the net's
-    current weights once per call (quantize.QuantizedTRUNet, stateless nets only)."""
+    current weights once per call (quantize.QuantizedTRUNet, stateless nets only).
+    fs: the sample rate of ``x``.  At another rate than 16 kHz the audio is resampled to 16 kHz on the GPU
+    (resample.resample), enhanced, resampled back and cut to exactly each input's length; the band above 8 kHz is not
+    restored.  Every utterance then needs at least 257 samples at 16 kHz."""
     if path not in PATHS:
         raise ValueError("path must be one of %s, got %r" % (PATHS, path))
     if max_frames is None:
@@ -120,6 +124,8 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
         raise L.TrunetHipError("enhance is an inference path: call net.eval() first")
     if net.use_tgru and path in ("folded", "int8"):
         raise ValueError("use_tgru runs the layer kernels (frames_per_seq): path=%r carries no sequence" % path)
+    if fs != SAMPLE_RATE:
+        return _enhance_at(net, x, lengths, beta, max_frames, path, fs)
     xs, width = _inputs(x, lengths)
     for b, t in enumerate(xs):
         if t.shape[0] < MIN_SAMPLES:
@@ -170,6 +176,29 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto"):
     Y = torch.zeros((pk.B, width), device=dev, dtype=torch.float32)
     for b, (s0, n) in enumerate(zip(pk.offs[0, :-1].tolist(), pk.lens)):
         Y[b, :n] = den[s0:s0 + n]
+    return Y
+
+
+def _enhance_at(net, x, lengths, beta, max_frames, path, fs):
+    """enhance() for audio at ``fs``: resample -> enhance at 16 kHz -> resample back -> cut to the input lengths.
+    ceil(ceil(L p / q) q / p) >= L, so there is always enough to cut."""
+    from . import resample as R
+    p, q = R.ratio(fs, SAMPLE_RATE)
+    xs, width = _inputs(x, lengths)
+    for b, t in enumerate(xs):
+        if R.out_length(t.shape[0], p, q) < MIN_SAMPLES:
+            raise ValueError("utterance %d has %d samples at %d Hz, %d at %d Hz; at least %d are needed there (reflect "
+                             "padding of the first frame)" % (b, t.shape[0], fs, R.out_length(t.shape[0], p, q),
+                                                              SAMPLE_RATE, MIN_SAMPLES))
+    lens = [int(t.shape[0]) for t in xs]
+    down = R.resample(xs, fs, SAMPLE_RATE)
+    den = enhance(net, down, beta=beta, max_frames=max_frames, path=path)
+    up = R.resample(den, SAMPLE_RATE, fs)
+    if width is None:
+        return [y[:n] for y, n in zip(up, lens)]
+    Y = torch.zeros((len(xs), width), device=up[0].device if up else x.device, dtype=torch.float32)
+    for b, (y, n) in enumerate(zip(up, lens)):
+        Y[b, :n] = y[:n]
     return Y
 
 
@@ -268,7 +297,10 @@ def _batches(lens, max_samples):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m tinyrecurrentunet_amd.enhance",
-                                 description="Denoise every 16 kHz *.wav of a folder with a trained TRU-Net (HIP, MI355X).")
+                                 description="Denoise every 16 kHz *.wav of a folder with a trained TRU-Net (HIP, MI355X).  "
+                                             "With --resample, files at other rates are resampled to 16 kHz on the GPU, "
+                                             "denoised and written back at their own rate; the band above 8 kHz is not "
+                                             "restored.")
     ap.add_argument("--checkpoint", required=True, help="train.py checkpoint ({'model_state_dict': ...}) or a state_dict")
     ap.add_argument("--input-size", type=int, choices=(3, 4), required=True, help="feature channels the net was trained on")
     ap.add_argument("--use-tgru", action="store_true", help="the net was trained with the time-recurrent block")
@@ -276,27 +308,43 @@ def main(argv=None):
     ap.add_argument("--out", dest="outdir", required=True, help="folder for the denoised int16 *.wav (same names)")
     ap.add_argument("--max-seconds", type=float, default=600.0, help="audio per enhance() call (default 600 s)")
     ap.add_argument("--path", choices=PATHS, default="auto", help="network path (default auto)")
+    ap.add_argument("--resample", action="store_true",
+                    help="accept files at other rates than 16 kHz (8 to 96 kHz): resample to 16 kHz, denoise, resample "
+                         "back; every file keeps its rate and sample count, the band above 8 kHz is not restored")
     args = ap.parse_args(argv)
 
     from scipy.io.wavfile import write as wavwrite
     from .dataset import _read_wav
     names = sorted(f for f in os.listdir(args.indir) if f.lower().endswith(".wav"))
-    xs = []
+    xs, rates = [], []
     for nm in names:
         x, sr = _read_wav(os.path.join(args.indir, nm))
         if sr != SAMPLE_RATE:
-            raise SystemExit("%s: %d Hz; the network runs at %d Hz (no resampling)" % (nm, sr, SAMPLE_RATE))
-        if x.shape[0] < MIN_SAMPLES:
+            if not args.resample:
+                raise SystemExit("%s: %d Hz; the network runs at %d Hz (no resampling)" % (nm, sr, SAMPLE_RATE))
+            from .resample import ratio, out_length
+            try:
+                p, q = ratio(sr, SAMPLE_RATE)
+            except ValueError as e:
+                raise SystemExit("%s: %s" % (nm, e))
+            if out_length(x.shape[0], p, q) < MIN_SAMPLES:
+                raise SystemExit("%s: %d samples at %d Hz, at least %d are needed at %d Hz"
+                                 % (nm, x.shape[0], sr, MIN_SAMPLES, SAMPLE_RATE))
+        elif x.shape[0] < MIN_SAMPLES:
             raise SystemExit("%s: %d samples, at least %d are needed" % (nm, x.shape[0], MIN_SAMPLES))
         xs.append(x)
+        rates.append(sr)
     net = load_net(args.checkpoint, args.input_size, args.use_tgru)
     os.makedirs(args.outdir, exist_ok=True)
-    max_samples = max(1, int(math.floor(args.max_seconds * SAMPLE_RATE)))
-    for idx in _batches([x.shape[0] for x in xs], max_samples):
-        ys = enhance(net, [xs[i].cuda() for i in idx], path=args.path)
-        for i, y in zip(idx, ys):
-            q = torch.clamp(torch.round(y * 32768.0), -32768, 32767).to(torch.int16).cpu().numpy()
-            wavwrite(os.path.join(args.outdir, names[i]), SAMPLE_RATE, q)
+    for rate in sorted(set(rates)):                       # --max-seconds counts seconds: samples at each group's rate
+        group = [i for i, r in enumerate(rates) if r == rate]
+        max_samples = max(1, int(math.floor(args.max_seconds * rate)))
+        for chunk in _batches([xs[i].shape[0] for i in group], max_samples):
+            idx = [group[k] for k in chunk]
+            ys = enhance(net, [xs[i].cuda() for i in idx], path=args.path, fs=rate)
+            for i, y in zip(idx, ys):
+                q16 = torch.clamp(torch.round(y * 32768.0), -32768, 32767).to(torch.int16).cpu().numpy()
+                wavwrite(os.path.join(args.outdir, names[i]), rate, q16)
     print("%d files -> %s" % (len(names), args.outdir))
 
 
