@@ -490,6 +490,27 @@ int trunet_resample_rational(const float* in, float* out, const int64_t* in_off,
                              const int64_t* tile_off, const float* table, int half, int K, int p, int q, int tile, int B,
                              int64_t total_in, int64_t total_out, int64_t total_tiles, int nsig, int taps_in_lds,
                              void* stream);
+/* trunet_resample_stream / trunet_resample_stream_commit (resample.py: StreamResampler): the same
+ * definition, taps table and per-output expression for sessions that arrive in packets; the outputs of a session, however it
+ * is cut, are bit for bit those of trunet_resample_rational on the whole.  hist (slots, K - 1): per slot the last K - 1
+ * samples of its session (K - 1 <= TRUNET_RS_STREAM_MAX_HISTORY); in (n_in): the packets of the call back to back; out
+ * (n_out); plan: DEVICE array (n_sess, TRUNET_RS_STREAM_INTS) int64, one record per listed session, distinct slots:
+ *   [0] slot   [1] N0: samples the session had before the call   [2] offset and [3] length n >= 0 of its packet in `in`
+ *   [4] m0: its first output of the call   [5] outputs   [6] their offset in `out`   [7] closing: outputs up to
+ *   ceil((N0 + n) p / q) with zeros right of the session, and no history is kept   [8], [9] its tiles [t0, t1) of the grid,
+ *   t1 - t0 = ceil(outputs / tile); n_tiles = the last t1.
+ * An open session owes the outputs below max(0, ceil(((N0 + n) p - half) / q)): they read no sample at or past N0 + n, and
+ * the next one reads none below N0 + n - (K - 1).  trunet_resample_stream: a workgroup per tile, reads hist only.
+ * trunet_resample_stream_commit, after it on the same stream: a workgroup per session, hist[slot] <- the last K - 1 samples
+ * of [hist[slot] | packet] (zeros left of sample 0).  TRUNET_EINVAL without a launch for anything the host can see; a record
+ * whose slot, packet, outputs or tiles lie outside slots, n_in, n_out or n_tiles is skipped by both kernels. */
+#define TRUNET_RS_STREAM_INTS 10
+#define TRUNET_RS_STREAM_MAX_HISTORY 20480
+int trunet_resample_stream(const float* hist, const float* in, float* out, const int64_t* plan, const float* table, int half,
+                           int K, int p, int q, int tile, int n_sess, int slots, int64_t n_in, int64_t n_out, int64_t n_tiles,
+                           int taps_in_lds, void* stream);
+int trunet_resample_stream_commit(float* hist, const float* in, const int64_t* plan, int half, int K, int p, int q, int n_sess,
+                                  int slots, int64_t n_in, void* stream);
 size_t trunet_stoi_workspace_bytes(int B, int64_t total_frames, int64_t total_segments);
 int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, const int64_t* frame_off, const int64_t* seg_off,
                        const int64_t* chunk_off, const float* window, const int* band_edges, const float* tw512,

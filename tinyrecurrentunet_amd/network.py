@@ -281,7 +281,8 @@ class TRUNet(nn.Module):
 
     def stream_pool(self, slots, **kw):
         """A ``streaming.StreamPool`` of ``slots`` independent streaming sessions on this network (eval mode): sessions open,
-        step, pause and close on their own, at any length from 257 samples; see the class for ``tgru`` / ``beta`` / ``int8``."""
+        step, pause and close on their own, at any length from 257 samples; see the class for ``tgru`` / ``beta`` / ``int8`` /
+        ``fs`` (packets at 8 to 96 kHz, resampled on the GPU)."""
         from .streaming import StreamPool
         return StreamPool(self, slots, **kw)
 

@@ -35,6 +35,7 @@ from . import _lib as L
 from ._lib import check, ptr
 
 N_FFT, HOP, BINS = 512, 128, 257
+SAMPLE_RATE = 16000                   # the network's rate (= enhance.SAMPLE_RATE)
 PCEN = dict(eps=1e-6, s=0.025, alpha=0.98, delta=2.0, r=0.5)     # dataset.py:56 defaults
 
 
@@ -368,7 +369,7 @@ class SlotAllocator:
 class StreamPool:
     """A fixed number of independent streaming sessions on the single-launch forward.
 
-        pool = StreamPool(net, slots, tgru=None, beta=0.5, int8=False)     # net in eval mode on the GPU; tgru None: net.use_tgru
+        pool = StreamPool(net, slots, tgru=None, beta=0.5, int8=False, fs=16000)   # net in eval mode on the GPU; tgru None: net.use_tgru
         ids = pool.open(n)                      # n free slot ids
         out, valid = pool.step(chunks, ids)     # chunks (n, 128) fp32 cuda; ids: n distinct open slots
         rest = pool.close(ids, tails)           # list of 1-D tensors; tails[i]: the 0..127 last samples of session i, or None
@@ -412,15 +413,29 @@ class StreamPool:
     ``net.fold_max_frames`` rows per launch either way), trunet_stream_feed_mask_istft (per frame), trunet_stream_feed_ola
     (per session: overlap-add in frame order).  No synchronisation with the device, one copy of the plan per call.  ``step``
     and ``feed`` may alternate on a session while nothing is pending; ``step``, or ``close`` with a tail, on a session with
-    pending samples is a ValueError that changes nothing."""
+    pending samples is a ValueError that changes nothing.
 
-    def __init__(self, net, slots, tgru=None, beta=0.5, int8=False):
+    ``fs`` (``pool.fs``): the sample rate of the packets ``feed`` takes and returns, 8 to 96 kHz (``resample.ratio``).  At
+    another rate than 16 kHz the pool owns two ``resample.StreamResampler`` over its slots, ``fs`` -> 16 kHz and back
+    (DESIGN section 3m): ``feed`` down-resamples the packets, runs the 16 kHz pass above on what became ready and
+    up-resamples what it returned; ``close(ids)`` flushes the down-resampler into a last 16 kHz feed, runs the 16 kHz
+    close, pushes both results through the up-resampler, closes it and cuts each session to the number of samples it was
+    fed (``enhance``'s rule at another rate).  A session of L samples at ``fs`` is bit for bit
+    ``resample(ys16, 16000, fs)[:L]``, ``ys16`` what a 16 kHz pool returns for ``resample(x, fs, 16000)``, however it is
+    cut into packets, and needs ceil(L 16000 / fs) >= 257: ``close`` raises ValueError below that, and the session and its
+    call-mates stay open and unchanged.  Each resampler adds a look-ahead of 16 samples at the lower of its two rates (1
+    ms each way at 48 kHz) to the four hops of the 16 kHz path.  ``step`` and ``close`` with a non-empty tail take 16
+    kHz hops and are a ValueError at another rate; ``pending`` and ``hops`` keep their 16 kHz meaning; ``open`` and
+    ``abort`` reset both resamplers' counters of the slot.  The band above 8 kHz is not restored.  With the default ``fs``
+    nothing changes.  ``AudioStream`` stays at 16 kHz."""
+
+    def __init__(self, net, slots, tgru=None, beta=0.5, int8=False, fs=SAMPLE_RATE):
         if net.training:
             raise L.TrunetHipError("StreamPool is an inference path: call net.eval() first")
         dev = next(net.parameters()).device
         if dev.type != "cuda":
             raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: the network sits on %s" % dev)
-        self._alloc = SlotAllocator(slots)
+        self._host_init(slots, fs, dev)
         self.tgru = bool(net.use_tgru if tgru is None else tgru)
         self.net, self.beta, self.dev = net, float(beta), dev
         self.C = net.encoder[0].StandardConv1d[0].in_channels
@@ -441,8 +456,21 @@ class StreamPool:
         self.h = self.run.new_state(S, dev) if self.tgru else None           # TGRU state (slots, 128, 16)
         self.fifo = z(S, HOP)                                    # feed(): the 0..127 samples that wait for their hop to fill
         self.tw = L.twiddles(N_FFT, dev)
+
+    def _host_init(self, slots, fs, dev):
+        """the host side of a pool: the slot allocator, the per-slot counters and, at another rate than 16 kHz, the two
+        stream resamplers (whose device buffers come with their first launch).  No device work."""
+        from . import resample as R
+        R.ratio(fs, SAMPLE_RATE)
+        self._alloc = SlotAllocator(slots)
+        S = self._alloc.capacity
+        self.fs, self.dev = int(fs), dev
         self._hops = np.zeros(S, dtype=np.int64)
         self._pend = np.zeros(S, dtype=np.int64)                 # samples in the FIFO, per slot
+        self._down = self._up = None
+        if self.fs != SAMPLE_RATE:
+            self._down = R.StreamResampler(self.fs, SAMPLE_RATE, S, dev)
+            self._up = R.StreamResampler(SAMPLE_RATE, self.fs, S, dev)
 
     # ---- host-side bookkeeping
     @property
@@ -468,11 +496,21 @@ class StreamPool:
         for i in ids:
             self._hops[i] = 0
             self._pend[i] = 0
+        self._reset_rate(ids)
         return ids
 
     def abort(self, ids):
         """Drop sessions without output; the slots are free again."""
-        self._alloc.release(self._ids(ids))
+        ids = self._ids(ids)
+        self._alloc.release(ids)
+        self._reset_rate(ids)
+
+    def _reset_rate(self, ids):
+        """another rate than 16 kHz: both resamplers' counters of the slots start at zero, and a slot whose count is zero
+        reads nothing of its history -- a session never sees the samples of the one before it"""
+        if self._down is not None and len(ids):
+            self._down.reset(ids)
+            self._up.reset(ids)
 
     def _ids(self, ids):
         """-> int64 array of distinct open slots; raises otherwise"""
@@ -531,6 +569,9 @@ class StreamPool:
         slots.  Returns (out (n, 128), valid (n,) CPU bool): row i is session ids[i]'s next 128 denoised samples where
         valid[i], zeros otherwise (its first three hops).  Never synchronises with the device."""
         ids = self._ids(ids)
+        if self._down is not None:
+            raise ValueError("step() takes hops of 128 samples at %d Hz; this pool runs at %d Hz, where feed() is the ingress"
+                             % (SAMPLE_RATE, self.fs))
         if not torch.is_tensor(chunks):
             raise ValueError("chunks: a (%d, %d) tensor, got %s" % (len(ids), HOP, type(chunks).__name__))
         if not chunks.is_cuda or chunks.device != self.dev:
@@ -556,38 +597,9 @@ class StreamPool:
                              % (what, ids[bad].tolist(), self._pend[ids][bad].tolist()))
 
     def _packets(self, packets, n):
-        """-> (list of 1-D device tensors to concatenate, lengths); host checks only"""
-        if isinstance(packets, tuple) and len(packets) == 2 and torch.is_tensor(packets[0]) and not (
-                torch.is_tensor(packets[1]) and packets[1].is_cuda):
-            flat, lens = packets
-            if torch.is_tensor(lens):
-                lens = lens.numpy()
-            lens = np.asarray(lens)
-            if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
-                raise ValueError("packet lengths: a 1-D sequence of host integers, got %s %s" % (lens.dtype, lens.shape))
-            parts, total = [flat], int(lens.astype(np.int64).sum()) if lens.size else 0
-            if flat.dim() != 1 or flat.shape[0] != total:
-                raise ValueError("the packed samples: a 1-D tensor of sum(lengths) = %d samples, got %s"
-                                 % (total, tuple(flat.shape)))
-        else:
-            if torch.is_tensor(packets) or not isinstance(packets, (list, tuple)):
-                raise ValueError("packets: a list of 1-D tensors, or (packed 1-D tensor, lengths), got %s"
-                                 % type(packets).__name__)
-            parts = list(packets)
-            for i, t in enumerate(parts):
-                if not torch.is_tensor(t) or t.dim() != 1:
-                    raise ValueError("packet %d: expected a 1-D tensor, got %s"
-                                     % (i, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-            lens = np.array([t.shape[0] for t in parts], dtype=np.int64)
-        if lens.shape[0] != n:
-            raise ValueError("%d packets for %d sessions" % (lens.shape[0], n))
-        for i, t in enumerate(parts):
-            if not t.is_cuda or t.device != self.dev:
-                raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: the pool sits on %s, packet %d is a %s tensor"
-                                       % (self.dev, i, t.device))
-            if not t.dtype.is_floating_point:
-                raise ValueError("packet %d: samples are floating point, got %s" % (i, t.dtype))
-        return parts, lens
+        """-> (list of 1-D device tensors to concatenate, int64 lengths); host checks only, the stream resampler's own"""
+        from . import resample as R
+        return R._stream_packets(packets, n, self.dev, "pool")
 
     def _net_rows(self, feat, rows, lo, hi, first):
         """the network on feature rows [lo, hi), at most net.fold_max_frames per launch; with the time-recurrent block the
@@ -619,9 +631,17 @@ class StreamPool:
         the plan of the call goes up in one copy."""
         ids = self._ids(ids)
         parts, lens = self._packets(packets, len(ids))
+        if self._down is not None:
+            return self._feed_at(parts, lens, ids)
         plan = plan_feed(self._hops, self._pend, lens, ids)
         if not len(ids):
             return []
+        out = self._feed16(plan, parts, ids)
+        return [out[HOP * int(o):HOP * int(o) + m] for o, m in zip(plan.out_off, plan.lengths)]
+
+    def _feed16(self, plan, parts, ids):
+        """the device side of ``feed``: the 16 kHz pass of ``plan`` over the packets ``parts`` -> the call's output, the
+        sessions' new samples back to back in the order of ``ids``"""
         lib, st, p, dev = L.lib(), L.stream(), PCEN, self.dev
         n_rows, n_sess, S = len(plan.rows), len(plan.sess), self.capacity
         samples = None
@@ -656,7 +676,56 @@ class StreamPool:
                   "stream_feed_ola")
         self._hops[ids] = plan.hops
         self._pend[ids] = plan.pending
-        return [out[HOP * int(o):HOP * int(o) + m] for o, m in zip(plan.out_off, plan.lengths)]
+        return out
+
+    # ---- another rate than 16 kHz: a stream resampler on either side of the 16 kHz pass
+    def _feed_at(self, parts, lens, ids):
+        """``feed`` at ``fs``: down-resample, the 16 kHz pass on what became ready, up-resample what it returned.  The three
+        plans are made before the first launch, so a refusal leaves every session as it was."""
+        down, up = self._down, self._up
+        pd = down.plan(lens, ids)
+        p16 = plan_feed(self._hops, self._pend, np.asarray(pd.lengths, dtype=np.int64), ids)
+        pu = up.plan(np.asarray(p16.lengths, dtype=np.int64), ids)
+        if not len(ids):
+            return []
+        x16 = down.run(pd, down._cat(parts, pd.n_in), ids)
+        y16 = self._feed16(p16, [x16], ids)
+        y = up.run(pu, y16 if pu.n_in else None, ids)
+        return list(torch.split(y, pu.lengths))                 # back to back in the order of ids
+
+    def _close_at(self, ids, tails):
+        """``close`` at ``fs``: the down-resampler's last outputs go through a last 16 kHz feed, the 16 kHz close follows, and
+        the up-resampler closes on both; each session is cut to the number of samples it was fed (``enhance``'s rule at
+        another rate: ceil(ceil(L p / q) q / p) >= L, so there is always enough to cut)."""
+        tails = None if tails is None else list(tails)
+        if tails is not None and len(tails) != len(ids):
+            raise ValueError("%d tails for %d sessions" % (len(tails), len(ids)))
+        if tails is not None and any(t is not None and (not torch.is_tensor(t) or t.numel()) for t in tails):
+            raise ValueError("close() takes tails at %d Hz; this pool runs at %d Hz, where feed() is the ingress and the "
+                             "samples that wait are the tail" % (SAMPLE_RATE, self.fs))
+        down, up = self._down, self._up
+        fed = down._recv[ids].copy()
+        pd = down.plan(np.zeros(len(ids), dtype=np.int64), ids, True)
+        L16 = HOP * self._hops[ids] + self._pend[ids] + np.asarray(pd.lengths, dtype=np.int64)     # = ceil(fed p / q)
+        if (L16 < MIN_SAMPLES).any():
+            i = int(np.argmax(L16 < MIN_SAMPLES))
+            raise ValueError("session %d has %d samples at %d Hz, %d at %d Hz; at least %d are needed there (reflect padding "
+                             "of the first frame)" % (ids[i], fed[i], self.fs, L16[i], SAMPLE_RATE, MIN_SAMPLES))
+        p16 = plan_feed(self._hops, self._pend, np.asarray(pd.lengths, dtype=np.int64), ids)
+        pc = plan_close(p16.hops, p16.pending, ids)
+        both = np.asarray(p16.lengths, dtype=np.int64) + np.asarray(pc.lengths, dtype=np.int64)
+        pu = up.plan(both, ids, True)
+        if not len(ids):
+            return []
+        sent = up._emit[ids].copy()
+        x16 = down.run(pd, None, ids)
+        a = self._feed16(p16, [x16], ids)
+        b = self._close16(ids, [None] * len(ids))
+        pieces = []
+        for i, (o, m) in enumerate(zip(p16.out_off, p16.lengths)):
+            pieces += [a[HOP * int(o):HOP * int(o) + m], b[i]]
+        y = up.run(pu, torch.cat(pieces), ids)
+        return [y[o:o + min(m, int(n))] for o, m, n in zip(pu.out_off, pu.lengths, fed - sent)]
 
     @torch.no_grad()
     def close(self, ids, tails=None):
@@ -666,6 +735,11 @@ class StreamPool:
         and frees the slots.  ValueError for a session of fewer than 257 samples; it stays open, like every other session of
         the call."""
         ids = self._ids(ids)
+        if self._down is not None:
+            return self._close_at(ids, tails)
+        return self._close16(ids, tails)
+
+    def _close16(self, ids, tails):
         tails = [None] * len(ids) if tails is None else list(tails)
         if len(tails) != len(ids):
             raise ValueError("%d tails for %d sessions" % (len(tails), len(ids)))
