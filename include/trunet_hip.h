@@ -345,6 +345,22 @@ int trunet_mask_istft_fwd(const float* net_out, float* frames, float* audio, con
 int trunet_mask_istft_l1_nparts(int B, int L);
 int trunet_mask_istft_bwd(const float* g_audio, const float* net_out, float* g_net, const float* tw512, int B,
                           int T, int L, float beta, void* stream);
+/* The same stages against the layer kernels' own layout, so that a training step needs no transpose pass at the network's
+ * boundary: x, net_out and g_net are frames-last [C][257][NP] with frame n = b T + t in the last dimension, N = B T <= NP,
+ * NP a multiple of 256 (anything else is TRUNET_EINVAL, as are the arguments the siblings above refuse).  Every value is
+ * bit for bit what the sibling followed / preceded by trunet_to_frames_last / trunet_from_frames_last gives.
+ * trunet_stft_features_fl: x [C][257][NP]; columns n >= N of the channels it writes are zero; mag [257][NP] when non-NULL.
+ * trunet_pcen_fl: mag [257][NP] -> out = channel 1 of x ([257][NP]); columns n >= N are written as zero.
+ * trunet_mask_istft_fwd_fl: net_out [8][257][NP]; frames, audio, l1_partials as trunet_mask_istft_fwd.
+ * trunet_mask_istft_bwd_fl: g_net [8][257][NP]; columns n >= N are written as zero. */
+int trunet_stft_features_fl(const float* audio, float* x, float* mag, const float* tw512, int B, int L, int T, int C,
+                            int NP, void* stream);
+int trunet_pcen_fl(const float* mag, float* out, int B, int T, int NP, float eps, float s, float alpha, float delta,
+                   float r, void* stream);
+int trunet_mask_istft_fwd_fl(const float* net_out, float* frames, float* audio, const float* clean, float* l1_partials,
+                             const float* tw512, int B, int T, int L, int NP, float beta, void* stream);
+int trunet_mask_istft_bwd_fl(const float* g_audio, const float* net_out, float* g_net, const float* tw512, int B, int T,
+                             int L, int NP, float beta, void* stream);
 /* g[i] = scale[0] * sign(den[i] - clean[i])  (backward of nn.L1Loss, util.py:239) */
 int trunet_l1_grad(const float* den, const float* clean, const float* scale, float* g, int64_t n, void* stream);
 /* out[c] = sum_g partials[g*ncols + c] in fp64 (one fp32 rounding of the sum); nparts, ncols >= 1 */

@@ -197,6 +197,10 @@ def _declare(L):
         "trunet_mask_istft_fwd": [p, p, p, p, p, p, i, i, i, f, p],
         "trunet_mask_istft_l1_nparts": [i, i],
         "trunet_mask_istft_bwd": [p, p, p, p, i, i, i, f, p],
+        "trunet_stft_features_fl": [p, p, p, p, i, i, i, i, i, p],
+        "trunet_pcen_fl": [p, p, i, i, i, f, f, f, f, f, p],
+        "trunet_mask_istft_fwd_fl": [p, p, p, p, p, p, i, i, i, i, f, p],
+        "trunet_mask_istft_bwd_fl": [p, p, p, p, i, i, i, i, f, p],
         "trunet_l1_grad": [p, p, p, p, i64, p],
         "trunet_reduce_cols": [p, i, i, p, p],
         "trunet_stft_loss_fwd": [p, p, p, p, p, i, i, i, i, p],
@@ -329,6 +333,29 @@ def ptr16(t):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+FRAME_PAD = 256      # the layer kernels pad the frame dimension to a multiple of 256 (widest conv_gemm tile)
+
+
+def frames_padded(n):
+    return (n + FRAME_PAD - 1) // FRAME_PAD * FRAME_PAD
+
+
+class FramesLast:
+    """Hand-off of a tensor in the layer kernels' own layout between the feature front end, the network and the fused loss
+    node of ``util.loss_fn`` (internal): t [C][257][NP], the N real frames in columns 0 .. N-1, the padding columns zero.
+
+    ticket (a network output only): the tensor IS the recording workspace's output buffer, not a copy, so the next
+    recording forward overwrites it.  Its consumer reads it at once and may read it again in its backward only after
+    ``ticket.check()``, the workspace generation check that ``TRUNetEngine.backward`` makes for the saved activations."""
+
+    def __init__(self, t, N, ticket=None):
+        assert t.dim() == 3 and t.shape[2] == frames_padded(N), (tuple(t.shape), N)
+        self.t, self.N, self.ticket = t, N, ticket
+
+    is_cuda = property(lambda self: self.t.is_cuda)
+    device = property(lambda self: self.t.device)
 
 
 def make_seg(src0, nchan, L, pos_mul=1, pos_off=0, pos_div=1, woff=0, mode=PRO_NONE, src1=None, c0=None, c1=None,

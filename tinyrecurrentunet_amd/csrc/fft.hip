@@ -99,6 +99,17 @@ __device__ __forceinline__ float spectral_features(float re, float im, float& nm
     return mag;
 }
 
+// frames t0, t0 + 1 of utterance x (L samples, centred, reflect padding) as ONE complex sequence; a frame past T is zero
+__device__ __forceinline__ cpx load_audio_pair(const float* __restrict__ x, int t0, int T, int L, int i) {
+    const float va = x[reflect_idx(t0 * HOPF + i - NF / 2, L)];
+    const float vb = (t0 + 1 < T) ? x[reflect_idx((t0 + 1) * HOPF + i - NF / 2, L)] : 0.f;
+    return make_float2(va, vb);
+}
+
+__device__ __forceinline__ void stage_audio_pair(cpx* sa, const float* __restrict__ x, int t0, int T, int L) {
+    for (int i = threadIdx.x; i < NF; i += 256) sa[i] = load_audio_pair(x, t0, T, L, i);
+}
+
 // grid (ceil(T/2), B); feat: (B*T, C, 257); mag (optional): (B, T, 257)
 __global__ __launch_bounds__(256) void stft_features_kernel(const float* __restrict__ audio, float* __restrict__ feat,
                                                             float* __restrict__ mag_out, const cpx* __restrict__ tw,
@@ -106,12 +117,7 @@ __global__ __launch_bounds__(256) void stft_features_kernel(const float* __restr
     __shared__ cpx sa[NF], sb[NF];
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * 2;
-    const float* x = audio + (size_t)b * L;
-    for (int i = threadIdx.x; i < NF; i += 256) {
-        const float va = x[reflect_idx(t0 * HOPF + i - NF / 2, L)];
-        const float vb = (t0 + 1 < T) ? x[reflect_idx((t0 + 1) * HOPF + i - NF / 2, L)] : 0.f;
-        sa[i] = make_float2(va, vb);
-    }
+    stage_audio_pair(sa, audio + (size_t)b * L, t0, T, L);
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx X[2];
@@ -209,6 +215,25 @@ __device__ __forceinline__ MaskVals mask_vals(const float* o, size_t cs, float b
     return v;
 }
 
+// masked spectrum X = M e^{j phi_m} of bin k from the 8 channels at o (channel stride cs); a frame that does not exist
+// (`valid` false: o is not read) is zero
+__device__ __forceinline__ cpx masked_bin(const float* o, size_t cs, int k, bool valid, float beta) {
+    cpx X = make_float2(0.f, 0.f);
+    if (valid) {
+        const MaskVals v = mask_vals(o, cs, beta);
+        const float M = v.S * v.A;
+        X = make_float2(M * v.cm, M * v.sm);
+    }
+    if (k == 0 || k == NF / 2) X.y = 0.f;     // c2r ignores the imaginary part of DC / Nyquist
+    return X;
+}
+
+// bin k of two half spectra as one complex sequence: Z = Xa_full + j Xb_full (Hermitian extensions)
+__device__ __forceinline__ void pack_pair(cpx* sa, int k, cpx Xa, cpx Xb) {
+    sa[k] = make_float2(Xa.x - Xb.y, Xa.y + Xb.x);
+    if (k > 0 && k < NF / 2) sa[NF - k] = make_float2(Xa.x + Xb.y, -Xa.y + Xb.x);
+}
+
 // grid (ceil(T/2), B); out_net: (B*T, 8, 257); frames: (B, T, 512) time-domain frames (irfft, 1/512)
 __global__ __launch_bounds__(256) void mask_istft_frames_kernel(const float* __restrict__ net_out,
                                                                 float* __restrict__ frames, const cpx* __restrict__ tw,
@@ -220,18 +245,10 @@ __global__ __launch_bounds__(256) void mask_istft_frames_kernel(const float* __r
         cpx X[2];
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
-            X[f] = make_float2(0.f, 0.f);
             const int t = t0 + f;
-            if (t < T) {
-                const MaskVals v = mask_vals(net_out + (size_t)(b * T + t) * 8 * BINS + k, BINS, beta);
-                const float M = v.S * v.A;
-                X[f] = make_float2(M * v.cm, M * v.sm);
-            }
-            if (k == 0 || k == NF / 2) X[f].y = 0.f;     // c2r ignores the imaginary part of DC / Nyquist
+            X[f] = masked_bin(net_out + (size_t)(b * T + t) * 8 * BINS + k, BINS, k, t < T, beta);
         }
-        // Z = Xa_full + j Xb_full (Hermitian extensions)
-        sa[k] = make_float2(X[0].x - X[1].y, X[0].y + X[1].x);
-        if (k > 0 && k < NF / 2) sa[NF - k] = make_float2(X[0].x + X[1].y, -X[0].y + X[1].x);
+        pack_pair(sa, k, X[0], X[1]);
     }
     const cpx* z = fft_lds_t<9, true>(sa, sb, tw);
     for (int i = threadIdx.x; i < NF; i += 256) {
@@ -283,6 +300,50 @@ __global__ void l1_grad_kernel(const float* __restrict__ den, const float* __res
     g[i] = (d > 0.f) ? scale[0] : ((d < 0.f) ? -scale[0] : 0.f);
 }
 
+// the windowed cotangent of frames t0, t0 + 1 of one utterance (g: its L samples of d loss / d audio) as ONE complex sequence
+__device__ __forceinline__ cpx load_grad_pair(const float* __restrict__ g, int t0, int T, int L, int i) {
+    float v[2] = {0.f, 0.f};
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+        const int t = t0 + f;
+        const int p = t * HOPF + i;
+        const int j = p - NF / 2;
+        if (t < T && j >= 0 && j < L) v[f] = g[j] / ola_env(p, T);
+    }
+    return make_float2(v[0], v[1]);
+}
+
+__device__ __forceinline__ void stage_grad_pair(cpx* sa, const float* __restrict__ g, int t0, int T, int L) {
+    for (int i = threadIdx.x; i < NF; i += 256) sa[i] = load_grad_pair(g, t0, T, L, i);
+}
+
+// bin k of one frame: G = its bin of the transformed cotangent, o = the 8 net-output channels, g = their gradients
+// (both with channel stride cs)
+__device__ __forceinline__ void mask_bwd_bin(const float* __restrict__ o, float* __restrict__ g, size_t cs, cpx G, int k,
+                                             float beta) {
+    const float wk = (k == 0 || k == NF / 2) ? (1.f / NF) : (2.f / NF);
+    const MaskVals v = mask_vals(o, cs, beta);
+    const float dRe = wk * G.x;
+    const float dIm = (k == 0 || k == NF / 2) ? 0.f : wk * G.y;
+    const float M = v.S * v.A;
+    const float dM = dRe * v.cm + dIm * v.sm;
+    float dpm = M * (dIm * v.cm - dRe * v.sm);
+    const float du = dM * v.A * v.S * (1.f - v.S);
+    dpm += beta * du;
+    const float dpn = -beta * du;
+    const float dA = dM * v.S;
+    const float dc0 = (v.c0 >= -1.f && v.c0 <= 1.f) ? dA * v.A * 2.5f * 2.302585092994046f : 0.f;
+    const float c2 = o[2 * cs], c3 = o[3 * cs], c6 = o[6 * cs], c7 = o[7 * cs];
+    g[0] = dc0;
+    g[1 * cs] = 0.f;
+    g[2 * cs] = (v.r2m > 0.f) ? dpm * c3 / v.r2m : 0.f;
+    g[3 * cs] = (v.r2m > 0.f) ? -dpm * c2 / v.r2m : 0.f;
+    g[4 * cs] = 0.f;
+    g[5 * cs] = 0.f;
+    g[6 * cs] = (v.r2n > 0.f) ? dpn * c7 / v.r2n : 0.f;
+    g[7 * cs] = (v.r2n > 0.f) ? -dpn * c6 / v.r2n : 0.f;
+}
+
 // backward of mask + iSTFT: g_audio (B, L) -> g_net (B*T, 8, 257)
 __global__ __launch_bounds__(256) void mask_istft_bwd_kernel(const float* __restrict__ g_audio,
                                                              const float* __restrict__ net_out,
@@ -291,50 +352,237 @@ __global__ __launch_bounds__(256) void mask_istft_bwd_kernel(const float* __rest
     __shared__ cpx sa[NF], sb[NF];
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * 2;
-    for (int i = threadIdx.x; i < NF; i += 256) {
-        float v[2] = {0.f, 0.f};
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            const int t = t0 + f;
-            const int p = t * HOPF + i;
-            const int j = p - NF / 2;
-            if (t < T && j >= 0 && j < L) v[f] = g_audio[(size_t)b * L + j] / ola_env(p, T);
-        }
-        sa[i] = make_float2(v[0], v[1]);
-    }
+    stage_grad_pair(sa, g_audio + (size_t)b * L, t0, T, L);
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx G[2];
         split_pair(Z, k, NF, G[0], G[1]);
-        const float wk = (k == 0 || k == NF / 2) ? (1.f / NF) : (2.f / NF);
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             const int t = t0 + f;
             if (t >= T) continue;
             const size_t base = (size_t)(b * T + t) * 8 * BINS + k;
-            const float* o = net_out + base;
-            const MaskVals v = mask_vals(o, BINS, beta);
-            const float dRe = wk * G[f].x;
-            const float dIm = (k == 0 || k == NF / 2) ? 0.f : wk * G[f].y;
-            const float M = v.S * v.A;
-            const float dM = dRe * v.cm + dIm * v.sm;
-            float dpm = M * (dIm * v.cm - dRe * v.sm);
-            const float du = dM * v.A * v.S * (1.f - v.S);
-            dpm += beta * du;
-            const float dpn = -beta * du;
-            const float dA = dM * v.S;
-            const float dc0 = (v.c0 >= -1.f && v.c0 <= 1.f) ? dA * v.A * 2.5f * 2.302585092994046f : 0.f;
-            const float c2 = o[2 * BINS], c3 = o[3 * BINS], c6 = o[6 * BINS], c7 = o[7 * BINS];
-            float* g = g_net + base;
-            g[0] = dc0;
-            g[1 * BINS] = 0.f;
-            g[2 * BINS] = (v.r2m > 0.f) ? dpm * c3 / v.r2m : 0.f;
-            g[3 * BINS] = (v.r2m > 0.f) ? -dpm * c2 / v.r2m : 0.f;
-            g[4 * BINS] = 0.f;
-            g[5 * BINS] = 0.f;
-            g[6 * BINS] = (v.r2n > 0.f) ? dpn * c7 / v.r2n : 0.f;
-            g[7 * BINS] = (v.r2n > 0.f) ? -dpn * c6 / v.r2n : 0.f;
+            mask_bwd_bin(net_out + base, g_net + base, BINS, G[f], k, beta);
         }
+    }
+}
+
+// ---------------------------------------------------------------- frames-last boundary
+// The same three stages against the network's own layout [C][257][NP], frame n = b T + t in the last dimension (columns
+// n >= N are padding), so that no transpose pass stands between them and the layer kernels.  A workgroup covers FLG consecutive
+// frames, utterance boundaries or not, and goes through LDS (sx: one complex value per frame and bin), so that every global
+// access to a frames-last row is FLG contiguous floats.  The transforms are the ones above, pair for pair: frames (t0 even,
+// t0 + 1) of one utterance share a transform, the last frame of an odd T has a zero partner.  A pair that straddles a group's
+// edge is transformed by both neighbours, each keeping its own frame.
+constexpr int FLG = 32;
+
+struct FlPair { int b, t0, next; };       // utterance, first frame of the pair, the first frame n after the pair
+
+__device__ __forceinline__ FlPair fl_pair(int n, int T) {
+    FlPair p;
+    p.b = n / T;
+    p.t0 = (n - p.b * T) & ~1;
+    p.next = p.b * T + min(p.t0 + 2, T);
+    return p;
+}
+
+// body(b, t0, slot, v0, v1) for every pair that holds one of the frames n0 .. min(n0 + FLG, N) - 1; slot = b T + t0 - n0 in
+// [-1, FLG).  v0, v1 = load(b, t0, i) for i = threadIdx.x and threadIdx.x + 256: what this thread stages of the pair from
+// global memory, requested one pair ahead, so that the round trip runs behind the previous pair's transform (a workgroup
+// makes up to 17 transforms one after the other, and its LDS leaves room for only two workgroups per CU to hide it).
+// The body stages into sa: fft_lds_t<9, .> leaves its result in sb and ends with a barrier, so sa is free by then, and a
+// body needs no barrier of its own before the next pair is staged.
+template <class Load, class Body>
+__device__ __forceinline__ void fl_each_pair(int n0, int N, int T, Load load, Body body) {
+    const int n1 = min(n0 + FLG, N);
+    if (n0 >= n1) return;
+    FlPair p = fl_pair(n0, T);
+    cpx v0 = load(p.b, p.t0, (int)threadIdx.x), v1 = load(p.b, p.t0, (int)threadIdx.x + 256);
+    for (;;) {
+        const FlPair cur = p;
+        const cpx c0 = v0, c1 = v1;
+        const bool more = cur.next < n1;
+        if (more) {
+            p = fl_pair(cur.next, T);
+            v0 = load(p.b, p.t0, (int)threadIdx.x);
+            v1 = load(p.b, p.t0, (int)threadIdx.x + 256);
+        }
+        body(cur.b, cur.t0, cur.b * T + cur.t0 - n0, c0, c1);
+        if (!more) break;
+    }
+}
+
+// The transforms of a workgroup run one after the other, so they take their twiddles from LDS: a global (L1) round trip in
+// every radix-4 stage, which eight workgroups per CU hide in the kernels above, would be paid 4 x 17 times in a row here, and
+// its vmcnt wait would end the flight of the next pair's samples as well.  (fft_lds_t begins with a barrier.)
+__device__ __forceinline__ void fl_stage_twiddles(cpx* stw, const cpx* __restrict__ tw) {
+    if (threadIdx.x < NF / 2) stw[threadIdx.x] = tw[threadIdx.x];
+}
+
+// grid NP / FLG; x: [C][257][NP] (channel 1 of C = 4 is left for the PCEN kernels), mag (optional): [257][NP]; columns
+// n >= N of the channels written here are zero
+__global__ __launch_bounds__(256) void stft_features_fl_kernel(const float* __restrict__ audio, float* __restrict__ x,
+                                                               float* __restrict__ mag_out, const cpx* __restrict__ tw,
+                                                               int L, int T, int C, int N, int NP) {
+    __shared__ cpx sa[NF], sb[NF], stw[NF / 2];
+    __shared__ cpx sx[FLG][BINS];
+    const int n0 = blockIdx.x * FLG;
+    fl_stage_twiddles(stw, tw);
+    fl_each_pair(n0, N, T,
+                 [&](int b, int t0, int i) { return load_audio_pair(audio + (size_t)b * L, t0, T, L, i); },
+                 [&](int b, int t0, int slot, cpx v0, cpx v1) {
+        sa[threadIdx.x] = v0;
+        sa[threadIdx.x + 256] = v1;
+        const cpx* Z = fft_lds_t<9, false>(sa, sb, stw);
+        for (int k = threadIdx.x; k < BINS; k += 256) {
+            cpx X[2];
+            split_pair(Z, k, NF, X[0], X[1]);
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+                if (t0 + f < T && slot + f >= 0 && slot + f < FLG) sx[slot + f][k] = X[f];
+        }
+        if (Z != sb) __syncthreads();          // (folds away: the result lies in sb, and the transform is done with sa)
+    });
+    __syncthreads();
+    const int fn = threadIdx.x & (FLG - 1);
+    const int n = n0 + fn;
+    const size_t plane = (size_t)BINS * NP;
+#pragma unroll 4
+    for (int k = threadIdx.x / FLG; k < BINS; k += 256 / FLG) {
+        float nm = 0.f, sn = 0.f, cs = 0.f, mag = 0.f;
+        if (n < N) {
+            const cpx X = sx[fn][k];
+            mag = spectral_features(X.x, X.y, nm, sn, cs);
+        }
+        float* o = x + (size_t)k * NP + n;
+        o[0] = nm;
+        o[(size_t)(C - 2) * plane] = sn;
+        o[(size_t)(C - 1) * plane] = cs;
+        if (mag_out) mag_out[(size_t)k * NP + n] = mag;
+    }
+}
+
+// pcen_scan_kernel on mag [257][NP]: a row is contiguous in t, so the chunk is loaded along t and transposed in LDS (the
+// scan reads xs[t][bin]; 65 columns keep both directions free of bank conflicts).  out: channel 1 of x, [257][NP].
+constexpr int PCEN_FL_TC = 128;
+__global__ __launch_bounds__(256) void pcen_scan_fl_kernel(const float* __restrict__ mag, float* __restrict__ out, int T,
+                                                           int NP, float s) {
+    __shared__ float xs[PCEN_FL_TC][65];
+    const int tid = threadIdx.x;
+    const int kb = blockIdx.x * 64;
+    const size_t col0 = (size_t)blockIdx.y * T;
+    float M = 0.f;                          // carried by threads 0..63 (bin kb + tid)
+    for (int t0 = 0; t0 < T; t0 += PCEN_FL_TC) {
+        const int tc = min(PCEN_FL_TC, T - t0);
+        for (int i = tid; i < PCEN_FL_TC * 64; i += 256) {
+            const int t = i & (PCEN_FL_TC - 1), k = i / PCEN_FL_TC;
+            if (t < tc) xs[t][k] = (kb + k < BINS) ? mag[(size_t)(kb + k) * NP + col0 + t0 + t] : 0.f;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            for (int t = 0; t < tc; ++t) {
+                const float v = xs[t][tid];
+                M = (t0 + t == 0) ? s * v : (1.f - s) * M + s * v;
+                xs[t][tid] = M;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < PCEN_FL_TC * 64; i += 256) {
+            const int t = i & (PCEN_FL_TC - 1), k = i / PCEN_FL_TC;
+            if (t < tc && kb + k < BINS) out[(size_t)(kb + k) * NP + col0 + t0 + t] = xs[t][k];
+        }
+        __syncthreads();
+    }
+}
+
+// pcen_pow_kernel on [257][NP]: grid (NP / 256, 257); columns n >= N are written as zero
+__global__ __launch_bounds__(256) void pcen_pow_fl_kernel(const float* __restrict__ mag, float* __restrict__ out, int N,
+                                                          int NP, float eps, float alpha, float delta, float r, float dr) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const size_t i = (size_t)blockIdx.y * NP + n;
+    out[i] = (n < N) ? pcen_value(mag[i], out[i], eps, alpha, delta, r, dr) : 0.f;
+}
+
+// grid NP / FLG; net_out: [8][257][NP]; frames: (B, T, 512) as mask_istft_frames_kernel writes them
+__global__ __launch_bounds__(256) void mask_istft_frames_fl_kernel(const float* __restrict__ net_out,
+                                                                   float* __restrict__ frames, const cpx* __restrict__ tw,
+                                                                   int T, int N, int NP, float beta) {
+    __shared__ cpx sa[NF], sb[NF], stw[NF / 2];
+    __shared__ cpx sx[FLG + 2][BINS];          // rows 0 and FLG + 1: the frames n0 - 1 and n0 + FLG (partners across the edges)
+    const int n0 = blockIdx.x * FLG;
+    fl_stage_twiddles(stw, tw);
+    if (n0 >= N) return;
+    const size_t plane = (size_t)BINS * NP;
+    const int fn = threadIdx.x & (FLG - 1);
+    if (n0 + fn < N) {
+#pragma unroll 4                               // (registers are free at two workgroups per CU: several bins' loads in flight)
+        for (int k = threadIdx.x / FLG; k < BINS; k += 256 / FLG)
+            sx[1 + fn][k] = masked_bin(net_out + (size_t)k * NP + n0 + fn, plane, k, true, beta);
+    } else {
+        for (int k = threadIdx.x / FLG; k < BINS; k += 256 / FLG) sx[1 + fn][k] = masked_bin(nullptr, plane, k, false, beta);
+    }
+    for (int i = threadIdx.x; i < 2 * BINS; i += 256) {
+        const int side = i / BINS, k = i - side * BINS;
+        const int n = side ? n0 + FLG : n0 - 1;
+        const bool valid = n >= 0 && n < N;
+        sx[side ? FLG + 1 : 0][k] = masked_bin(net_out + (size_t)k * NP + (valid ? n : 0), plane, k, valid, beta);
+    }
+    __syncthreads();
+    fl_each_pair(n0, N, T, [](int, int, int) { return make_float2(0.f, 0.f); },      // nothing to stage from global memory
+                 [&](int b, int t0, int slot, cpx, cpx) {
+        for (int k = threadIdx.x; k < BINS; k += 256) {
+            cpx X1 = sx[slot + 2][k];
+            if (t0 + 1 >= T) X1 = make_float2(0.f, 0.f);          // (that row is the next utterance's first frame)
+            pack_pair(sa, k, sx[slot + 1][k], X1);
+        }
+        const cpx* z = fft_lds_t<9, true>(sa, sb, stw);
+        for (int i = threadIdx.x; i < NF; i += 256) {
+            const cpx v = z[i];
+            if (slot >= 0) frames[((size_t)b * T + t0) * NF + i] = v.x * (1.f / NF);
+            if (t0 + 1 < T && slot + 1 < FLG) frames[((size_t)b * T + t0 + 1) * NF + i] = v.y * (1.f / NF);
+        }
+        if (z != sb) __syncthreads();          // (folds away: the result lies in sb, and the transform is done with sa)
+    });
+}
+
+// grid NP / FLG; g_audio (B, L), net_out [8][257][NP] -> g_net [8][257][NP] with zero columns n >= N
+__global__ __launch_bounds__(256) void mask_istft_bwd_fl_kernel(const float* __restrict__ g_audio,
+                                                                const float* __restrict__ net_out,
+                                                                float* __restrict__ g_net, const cpx* __restrict__ tw,
+                                                                int T, int L, int N, int NP, float beta) {
+    __shared__ cpx sa[NF], sb[NF], stw[NF / 2];
+    __shared__ cpx sx[FLG][BINS];
+    const int n0 = blockIdx.x * FLG;
+    fl_stage_twiddles(stw, tw);
+    fl_each_pair(n0, N, T,
+                 [&](int b, int t0, int i) { return load_grad_pair(g_audio + (size_t)b * L, t0, T, L, i); },
+                 [&](int b, int t0, int slot, cpx v0, cpx v1) {
+        sa[threadIdx.x] = v0;
+        sa[threadIdx.x + 256] = v1;
+        const cpx* Z = fft_lds_t<9, false>(sa, sb, stw);
+        for (int k = threadIdx.x; k < BINS; k += 256) {
+            cpx G[2];
+            split_pair(Z, k, NF, G[0], G[1]);
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+                if (t0 + f < T && slot + f >= 0 && slot + f < FLG) sx[slot + f][k] = G[f];
+        }
+        if (Z != sb) __syncthreads();          // (folds away: the result lies in sb, and the transform is done with sa)
+    });
+    __syncthreads();
+    const int fn = threadIdx.x & (FLG - 1);
+    const int n = n0 + fn;
+    const size_t plane = (size_t)BINS * NP;
+    if (n < N) {
+#pragma unroll 4                               // (registers are free at two workgroups per CU: several bins' loads in flight)
+        for (int k = threadIdx.x / FLG; k < BINS; k += 256 / FLG) {
+            const size_t base = (size_t)k * NP + n;
+            mask_bwd_bin(net_out + base, g_net + base, plane, sx[fn][k], k, beta);
+        }
+    } else {
+        for (int k = threadIdx.x / FLG; k < BINS; k += 256 / FLG)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) g_net[(size_t)k * NP + n + c * plane] = 0.f;
     }
 }
 
@@ -1498,6 +1746,50 @@ extern "C" int trunet_mask_istft_bwd(const float* g_audio, const float* net_out,
                                      int T, int L, float beta, void* stream) {
     if (!g_audio || !net_out || !g_net || !tw512 || B <= 0 || T < 2 || L != (T - 1) * HOPF) return TRUNET_EINVAL;
     hipLaunchKernelGGL(mask_istft_bwd_kernel, dim3((T + 1) / 2, B), dim3(256), 0, ST, g_audio, net_out, g_net, (const cpx*)tw512, T, L, beta);
+    return trunet_launch_status();
+}
+
+// ---- frames-last boundary: x / net_out / g_net are [C][257][NP], N = B T frames, NP a multiple of 256 (the layer kernels' tile)
+static bool fl_shape_ok(int B, int T, int NP) {
+    return B > 0 && T > 0 && NP > 0 && NP % 256 == 0 && (int64_t)B * T <= NP;
+}
+
+extern "C" int trunet_stft_features_fl(const float* audio, float* x, float* mag, const float* tw512, int B, int L, int T,
+                                       int C, int NP, void* stream) {
+    if (!audio || !x || !tw512 || B <= 0 || L < NF / 2 + 1 || T != 1 + L / HOPF || (C != 3 && C != 4)) return TRUNET_EINVAL;
+    if (!fl_shape_ok(B, T, NP)) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stft_features_fl_kernel, dim3(NP / FLG), dim3(256), 0, ST, audio, x, mag, (const cpx*)tw512, L, T, C,
+                       B * T, NP);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_pcen_fl(const float* mag, float* out, int B, int T, int NP, float eps, float s, float alpha,
+                              float delta, float r, void* stream) {
+    if (!mag || !out || B <= 0 || T <= 0) return TRUNET_EINVAL;
+    if (!fl_shape_ok(B, T, NP)) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(pcen_scan_fl_kernel, dim3((BINS + 63) / 64, B), dim3(256), 0, ST, mag, out, T, NP, s);
+    hipLaunchKernelGGL(pcen_pow_fl_kernel, dim3(NP / 256, BINS), dim3(256), 0, ST, mag, out, B * T, NP, eps, alpha, delta, r,
+                       powf(delta, r));
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_mask_istft_fwd_fl(const float* net_out, float* frames, float* audio, const float* clean,
+                                        float* l1_partials, const float* tw512, int B, int T, int L, int NP, float beta,
+                                        void* stream) {
+    if (!net_out || !frames || !audio || !tw512 || B <= 0 || T < 2 || L != (T - 1) * HOPF) return TRUNET_EINVAL;
+    if (!fl_shape_ok(B, T, NP)) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(mask_istft_frames_fl_kernel, dim3(NP / FLG), dim3(256), 0, ST, net_out, frames, (const cpx*)tw512, T,
+                       B * T, NP, beta);
+    hipLaunchKernelGGL(ola_kernel, dim3((L + 255) / 256, B), dim3(256), 0, ST, frames, audio, clean, l1_partials, T, L);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_mask_istft_bwd_fl(const float* g_audio, const float* net_out, float* g_net, const float* tw512, int B,
+                                        int T, int L, int NP, float beta, void* stream) {
+    if (!g_audio || !net_out || !g_net || !tw512 || B <= 0 || T < 2 || L != (T - 1) * HOPF) return TRUNET_EINVAL;
+    if (!fl_shape_ok(B, T, NP)) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(mask_istft_bwd_fl_kernel, dim3(NP / FLG), dim3(256), 0, ST, g_audio, net_out, g_net, (const cpx*)tw512,
+                       T, L, B * T, NP, beta);
     return trunet_launch_status();
 }
 

@@ -33,14 +33,27 @@ def _need_gpu(x):
         raise L.TrunetHipError("tinyrecurrentunet_amd.dataset runs on MI355X only (got %s)" % x.device)
 
 
-def stft_features(audio_BL, pcen=False):
+def stft_features(audio_BL, pcen=False, _frames_last=False):
     """(B, L) audio -> (B*T, C, 257) features, C = 4 with PCEN (R2 order) else 3.  One launch per batch
-    (the reference loops per utterance, D11)."""
+    (the reference loops per utterance, D11).
+
+    _frames_last (internal, util.loss_fn): the same values as a ``_lib.FramesLast`` hand-off, [C][257][NP] with zero
+    padding columns -- the layout the network's first layer reads, so the network needs no transpose pass."""
     _need_gpu(audio_BL)
     audio_BL = audio_BL.contiguous().float()
     B, Ln = audio_BL.shape
     T = 1 + Ln // HOP
     C = 4 if pcen else 3
+    if _frames_last:
+        NP = L.frames_padded(B * T)
+        x = torch.empty((C, BINS, NP), device=audio_BL.device, dtype=torch.float32)
+        mag = torch.empty((BINS, NP), device=audio_BL.device, dtype=torch.float32) if pcen else None
+        tw = L.twiddles(N_FFT, audio_BL.device)
+        check(L.lib().trunet_stft_features_fl(ptr(audio_BL), ptr(x), ptr(mag), ptr(tw), B, Ln, T, C, NP, L.stream()),
+              "stft_features_fl")
+        if pcen:
+            check(L.lib().trunet_pcen_fl(ptr(mag), ptr(x[1]), B, T, NP, 1e-6, 0.025, 0.98, 2.0, 0.5, L.stream()), "pcen_fl")
+        return L.FramesLast(x, B * T)
     feat = torch.empty((B * T, C, BINS), device=audio_BL.device, dtype=torch.float32)
     mag = torch.empty((B, T, BINS), device=audio_BL.device, dtype=torch.float32) if pcen else None
     tw = L.twiddles(N_FFT, audio_BL.device)

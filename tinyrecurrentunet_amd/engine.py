@@ -26,7 +26,7 @@ from ._lib import (DG_ACCUM, DG_MASK, DG_PREZERO, DG_STATS, DG_STORE, EPI_ACCUM,
                    PRO_BNRELU, PRO_NONE, ConvtBwdArgs, GemmArgs, PwBwdArgs, WgradArgs, check, make_seg, ptr)
 
 F_BINS = 257
-FRAME_PAD = 256      # frames are padded to a multiple of 256 (widest conv_gemm tile)
+FRAME_PAD = L.FRAME_PAD      # frames are padded to a multiple of 256 (widest conv_gemm tile)
 BN_EPS = 1e-5
 BN_MOM = 0.1
 
@@ -161,6 +161,21 @@ class Act:
             return make_seg(self.t, self.C, self.L, pos_mul, pos_off, pos_div, woff, PRO_NONE)
         return make_seg(self.t, self.C, self.L, pos_mul, pos_off, pos_div, woff, PRO_BNRELU,
                         c0=self.bn.scale, c1=self.bn.shift)
+
+
+class OutTicket:
+    """Goes with a network output that is handed out frames-last (``_lib.FramesLast``): that tensor is the recording
+    workspace's own "z:dec5" buffer.  Design: no buffer of its own -- the fused loss node consumes the output before the next
+    recording forward (it reads it in its forward, and once more in its backward after ``check()``), so a second forward
+    before ``backward`` raises the same generation error there as it does for the saved activations.
+    cotangent: the consumer's gradient tensor [8][257][NP], whose padding columns it has written as zero; ``backward`` takes
+    exactly that tensor as it is and zeroes the padding of any other."""
+
+    def __init__(self):
+        self.w, self.gen, self.cotangent = None, None, None
+
+    def check(self):
+        TRUNetEngine._check_gen(self.w, self.gen)
 
 
 class Workspace:
@@ -892,12 +907,21 @@ class TRUNetEngine:
         state.steps += 1
         return self._pw(w, "tgru", [Act(state.h, Hh, Lg)], blk.conv[0], blk.conv[1], N, NP, False)
 
-    def forward(self, x, training, tgru_state=None, tgru_T=None, record=False):
+    def forward(self, x, training, tgru_state=None, tgru_T=None, record=False, ticket=None):
+        """x: (N, C_in, 257) features -> ((N, 8, 257), ctx for ``backward``).  Frames-last boundary (util.loss_fn): x a
+        ``_lib.FramesLast`` is read where it lies, and with ``ticket`` (an OutTicket) the output is returned as the
+        [8][257][NP] tensor the last layer wrote -- no transpose pass on either side."""
         net = self.net
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == F_BINS
-        x = x.contiguous()
-        N, Cin = x.shape[0], x.shape[1]
-        NP = ceil_to(N, FRAME_PAD)
+        fl_in = isinstance(x, L.FramesLast)
+        if fl_in:
+            xt, N = x.t, x.N
+            assert xt.is_cuda and xt.dtype == torch.float32 and xt.is_contiguous() and xt.shape[1] == F_BINS
+            Cin, NP = xt.shape[0], xt.shape[2]
+        else:
+            assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == F_BINS
+            x = x.contiguous()
+            N, Cin = x.shape[0], x.shape[1]
+            NP = ceil_to(N, FRAME_PAD)
         w = self.ws(NP, x.device, record)
         if record:
             w.gen += 1
@@ -905,8 +929,9 @@ class TRUNetEngine:
         st = L.stream()
         acts = {}
 
-        xt = w.get("x", (Cin, F_BINS, NP))
-        check(lib.trunet_to_frames_last(ptr(x), ptr(xt), N, Cin, F_BINS, NP, st), "to_frames_last")
+        if not fl_in:
+            xt = w.get("x", (Cin, F_BINS, NP))
+            check(lib.trunet_to_frames_last(ptr(x), ptr(xt), N, Cin, F_BINS, NP, st), "to_frames_last")
         c0 = net.encoder[0].StandardConv1d[0]
         assert c0.in_channels == Cin
         a0t = w.get("z:enc0", (64, 128, NP))
@@ -940,6 +965,9 @@ class TRUNetEngine:
                                                   x1_left=left)
             cur = acts["dec%d" % i] = self._convT(w, "dec%d" % i, cur, seq[3], seq[4] if i < 5 else None, N, NP,
                                                   training)
+        if ticket is not None:
+            ticket.w, ticket.gen = w, w.gen
+            return cur.t.detach(), (acts, N, NP, w, w.gen)      # (a fresh tensor object on the same buffer for autograd)
         out = torch.empty((N, cur.C, cur.L), device=x.device, dtype=torch.float32)
         check(lib.trunet_from_frames_last(ptr(cur.t), ptr(out), N, cur.C, cur.L, NP, st), "from_frames_last")
         return out, (acts, N, NP, w, w.gen)
@@ -1164,10 +1192,18 @@ class TRUNetEngine:
         self._fam(xa).wgrad(w, N=N, NP=NP, P=Lo, M=c0.out_channels, dz=dy, dz_L=Lo, dz_bn=None, W=c0.weight,
                             ldw_m=xa.C * k, ldw_c=k, segs=segs, grads=grads, bias=c0.bias)
 
-    def _bwd_entry(self, w, acts, gout, N, NP, grads):
+    def _bwd_entry(self, w, acts, gout, N, NP, grads, ticket=None):
         """The output cotangent (N, 8, 257) as the decoder's first upstream gradient (dy tensor, z tensor, BatchNorm state
-        of that z or None), and decoder.5's dy_pw when its transposed conv is already done here (else None)."""
+        of that z or None), and decoder.5's dy_pw when its transposed conv is already done here (else None).
+        ticket (the forward handed its output out frames-last): gout is [8][257][NP] already and is read where it lies."""
         last = acts["dec5"]
+        if ticket is not None:
+            assert tuple(gout.shape) == (last.C, last.L, NP)
+            own, ticket.cotangent = ticket.cotangent, None
+            if NP > N and not (own is not None and own.data_ptr() == gout.data_ptr()):
+                gout = gout.clone()              # somebody else's gradient: its padding columns are not known to be zero
+                gout[:, :, N:].zero_()
+            return (gout, last.t, None), None
         dyt = w.get("dy:dec5", (last.C, last.L, NP))
         check(L.lib().trunet_to_frames_last(ptr(gout), ptr(dyt), N, last.C, last.L, NP, L.stream()), "to_frames_last")
         return (dyt, last.t, None), None
@@ -1181,14 +1217,17 @@ class TRUNetEngine:
         self._bwd_fgru(w, N, NP, self.net.FGRU, up, acts["hout"], enc5, enc5, dy5, grads)
         return dy5, enc5.t, enc5.bn
 
-    def backward(self, ctx, gout):
-        """gout: (N, 8, 257) cotangent.  Returns {parameter tensor: gradient}."""
+    def backward(self, ctx, gout, ticket=None):
+        """gout: (N, 8, 257) cotangent ([8][257][NP] with the forward's ``ticket``).  Returns {parameter tensor: gradient}."""
         acts, N, NP, w, gen = ctx
         self._check_gen(w, gen)
         net = self.net
         grads = {}
         self._wg_begin(w)
-        up, dy_pw5 = self._bwd_entry(w, acts, gout.contiguous(), N, NP, grads)
+        if ticket is None:
+            up, dy_pw5 = self._bwd_entry(w, acts, gout.contiguous(), N, NP, grads)
+        else:
+            up, dy_pw5 = self._bwd_entry(w, acts, gout.contiguous().float(), N, NP, grads, ticket)
         # -------- decoder, last to first
         for i in range(5, -1, -1):
             seq = (net.decoder[i].LastTrCNN if i == 5 else net.decoder[i].TrCNN) if i > 0 else net.decoder[0].FirstTrCNN

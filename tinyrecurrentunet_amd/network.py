@@ -177,6 +177,27 @@ class _TRUNetFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads.get(p) for p in ctx.params)
 
 
+class _TRUNetFramesLastFn(torch.autograd.Function):
+    """_TRUNetFn with both ends in the layer kernels' layout (``_lib.FramesLast``, util.loss_fn): x [C_in][257][NP] holding
+    n frames -> [8][257][NP], the engine's own output buffer (``ticket``: engine.OutTicket); the cotangent comes back in the
+    same layout."""
+
+    @staticmethod
+    def forward(ctx, x, n, engine, training, ticket, *params):
+        out, ectx = engine.forward(_lib.FramesLast(x, n), training, record=training, ticket=ticket)
+        ctx.engine, ctx.ectx, ctx.params = engine, ectx, params
+        ctx.training, ctx.ticket = training, ticket
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.training:
+            raise _lib.TrunetHipError("backward through TRUNet in eval() mode is not supported "
+                                      "(BatchNorm running statistics); call net.train()")
+        grads = ctx.engine.backward(ctx.ectx, gout, ticket=ctx.ticket)
+        return (None, None, None, None, None) + tuple(grads.get(p) for p in ctx.params)
+
+
 class TRUNet(nn.Module):
     """Tiny Recurrent U-Net body: (N, C_in, 257) -> (N, 8, 257), N = frames.
 
@@ -294,8 +315,26 @@ class TRUNet(nn.Module):
     def _active_params(self):
         return [p for n, p in self.named_parameters() if self.use_tgru or not n.startswith("TGRU.")]
 
+    def _forward_frames_last(self, x):
+        """``forward`` on a ``_lib.FramesLast`` hand-off (internal, util.loss_fn): features [C_in][257][NP] in, the network
+        output [8][257][NP] out as a hand-off again, no transpose pass on either side.  fp32 engine without TGRU only."""
+        from .engine import OutTicket
+        if self.precision != "fp32" or self.use_tgru:
+            raise _lib.TrunetHipError("the frames-last boundary exists on the fp32 engine without use_tgru")
+        if self._engine is None:
+            object.__setattr__(self, "_engine", self._make_engine())
+        params = self._active_params()
+        ticket = OutTicket()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            out = _TRUNetFramesLastFn.apply(x.t, x.N, self._engine, self.training, ticket, *params)
+        else:
+            out, _ = self._engine.forward(x, self.training, ticket=ticket)
+        return _lib.FramesLast(out, x.N, ticket)
+
     def forward(self, x, frames_per_seq=None):
         _need_gpu(x)
+        if isinstance(x, _lib.FramesLast):
+            return self._forward_frames_last(x)
         if self._engine is None:
             object.__setattr__(self, "_engine", self._make_engine())
         T = None

@@ -77,17 +77,29 @@ FUSED_LOSS = os.environ.get("TRUNET_FUSED_LOSS", "1") != "0"
 _LOSS_SCRATCH = {}
 
 
+def _fl_boundary(net, plan):
+    """Frames-last boundary of the train step: the features are written, the network output is read and its cotangent is
+    written in the layer kernels' own layout [C][257][NP] (``_lib.FramesLast``), which takes the three transpose passes
+    between these stages out of the step and changes no value.  Taken when the fused loss node consumes the output, the net
+    is the fp32 engine in training mode without TGRU and autograd records; TRUNET_FL_BOUNDARY=0 (read per call) keeps the
+    (N, C, 257) tensors, as every other case does."""
+    return (plan is not None and os.environ.get("TRUNET_FL_BOUNDARY", "1") != "0" and hasattr(net, "_forward_frames_last")
+            and getattr(net, "precision", None) == "fp32" and not getattr(net, "use_tgru", False) and net.training
+            and torch.is_grad_enabled())
+
+
 class _FusedLossFn(torch.autograd.Function):
     """net output (B*T, 8, 257), clean (B, L) -> (loss, vals); vals = [loss, l1, stft_sc, stft_mag, ...] (no gradient).
     With ``wave`` (the time-domain terms of cos_loss.py) -> (loss, vals, wave vals): the terms are added
     to ``loss`` on the device by two more launches forward and one more backward; vals[0] stays the loss without them."""
 
     @staticmethod
-    def forward(ctx, net_out, clean, T, beta, stft_lambda, res, sc_lambda, mag_lambda, wave=None):
+    def forward(ctx, net_out, clean, T, beta, stft_lambda, res, sc_lambda, mag_lambda, wave=None, fl=None):
         # res: [(padded window, n, hop, win_length), ...] (empty: L1 only)
         # wave: None or (g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps), g = () without the cosine term
+        # fl: None, or the _lib.FramesLast hand-off whose tensor net_out is: [8][257][NP], the network's own output buffer
         net_out = net_out.contiguous()
-        B = net_out.shape[0] // T
+        B = (net_out.shape[0] if fl is None else fl.N) // T
         Ln = (T - 1) * HOP
         dev = net_out.device
         lib, st = L.lib(), L.stream()
@@ -96,8 +108,12 @@ class _FusedLossFn(torch.autograd.Function):
         npart = lib.trunet_mask_istft_l1_nparts(B, Ln)
         part = torch.empty(npart, device=dev, dtype=torch.float32)
         tw = L.twiddles(N_FFT, dev)
-        check(lib.trunet_mask_istft_fwd(ptr(net_out), ptr(frames), ptr(audio), ptr(clean), ptr(part), ptr(tw), B, T,
-                                        Ln, beta, st), "mask_istft_fwd")
+        if fl is None:
+            check(lib.trunet_mask_istft_fwd(ptr(net_out), ptr(frames), ptr(audio), ptr(clean), ptr(part), ptr(tw), B, T,
+                                            Ln, beta, st), "mask_istft_fwd")
+        else:
+            check(lib.trunet_mask_istft_fwd_fl(ptr(net_out), ptr(frames), ptr(audio), ptr(clean), ptr(part), ptr(tw), B, T,
+                                               Ln, net_out.shape[2], beta, st), "mask_istft_fwd_fl")
         a = L.LossArgs()
         a.l1_partials, a.n_l1, a.l1_count, a.nres = ptr(part), npart, float(B * Ln), len(res)
         a.sc_lambda, a.mag_lambda, a.stft_lambda = sc_lambda, mag_lambda, stft_lambda
@@ -125,7 +141,7 @@ class _FusedLossFn(torch.autograd.Function):
         loss = torch.empty((), device=dev, dtype=torch.float32)
         vals = torch.empty(5 + 2 * L.MAX_RES, device=dev, dtype=torch.float32)
         check(lib.trunet_loss_finalize(a, ptr(loss), ptr(vals), scratch.data_ptr(), st), "loss_finalize")
-        ctx.planes, ctx.T, ctx.beta, ctx.wave = planes, T, beta, None
+        ctx.planes, ctx.T, ctx.beta, ctx.wave, ctx.fl = planes, T, beta, None, fl
         if wave is None:
             ctx.save_for_backward(net_out, clean, audio, tw, vals)
             ctx.mark_non_differentiable(vals)
@@ -154,9 +170,18 @@ class _FusedLossFn(torch.autograd.Function):
             from . import cos_loss as cl
             cl.wave_backward(audio, clean, ctx.wave, ctx.saved_tensors[5], g_loss, g)
         g_net = torch.empty_like(net_out)
-        check(lib.trunet_mask_istft_bwd(ptr(g), ptr(net_out), ptr(g_net), ptr(tw), B, ctx.T, Ln, ctx.beta, st), "mask_istft_bwd")
+        if ctx.fl is None:
+            check(lib.trunet_mask_istft_bwd(ptr(g), ptr(net_out), ptr(g_net), ptr(tw), B, ctx.T, Ln, ctx.beta, st), "mask_istft_bwd")
+        else:
+            # net_out is the engine's output buffer itself: refuse to read it once a later recording forward has overwritten
+            # it.  The kernel writes the padding columns of g_net as zero, which the ticket tells the engine's backward.
+            ticket = ctx.fl.ticket
+            ticket.check()
+            check(lib.trunet_mask_istft_bwd_fl(ptr(g), ptr(net_out), ptr(g_net), ptr(tw), B, ctx.T, Ln, net_out.shape[2],
+                                               ctx.beta, st), "mask_istft_bwd_fl")
+            ticket.cotangent = g_net
         ctx.planes = None
-        return g_net, None, None, None, None, None, None, None, None
+        return g_net, None, None, None, None, None, None, None, None, None
 
 
 def _fused_loss_plan(mrstftloss, stft_lambda, dev):
@@ -207,19 +232,26 @@ def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, cos
     noisy = noisy_audio[:, 0].contiguous()
     if pcen is None:
         pcen = net.encoder[0].StandardConv1d[0].in_channels == 4
-    feats = ds.stft_features(noisy, pcen=pcen)
-    T = feats.shape[0] // noisy.shape[0]
-    # use_tgru (extension): the time-recurrent block needs to know where utterances begin
-    out = net(feats, frames_per_seq=T) if getattr(net, "use_tgru", False) else net(feats)
-    plan = _fused_loss_plan(mrstftloss, stft_lambda, out.device) if out.is_cuda else None
+    plan = _fused_loss_plan(mrstftloss, stft_lambda, noisy.device) if noisy.is_cuda else None
+    fl = None
+    if _fl_boundary(net, plan):
+        fl = net(ds.stft_features(noisy, pcen=pcen, _frames_last=True))
+        out, T = fl.t, fl.N // noisy.shape[0]
+    else:
+        feats = ds.stft_features(noisy, pcen=pcen)
+        T = feats.shape[0] // noisy.shape[0]
+        # use_tgru (extension): the time-recurrent block needs to know where utterances begin
+        out = net(feats, frames_per_seq=T) if getattr(net, "use_tgru", False) else net(feats)
     wave = _wave_terms(cos_lambda, cos_config, si_sdr_lambda, si_sdr_eps)
     if plan is not None:
         fused = (out, clean.float(), T, 0.5, float(stft_lambda) if plan else 0.0, plan,
                  float(mrstftloss.sc_lambda) if plan else 0.0, float(mrstftloss.mag_lambda) if plan else 0.0)
-        if wave is None:
+        if wave is None and fl is None:
             loss, vals = _FusedLossFn.apply(*fused)
+        elif wave is None:
+            loss, vals = _FusedLossFn.apply(*fused, None, fl)
         else:
-            loss, vals, wvals = _FusedLossFn.apply(*fused, wave)
+            loss, vals, wvals = _FusedLossFn.apply(*fused, wave, fl)
         output_dic = {"l1": vals[1]}
         if plan:
             output_dic["stft_sc"], output_dic["stft_mag"] = vals[2], vals[3]
