@@ -519,7 +519,12 @@ int trunet_resample_rational(const float* in, float* out, const int64_t* in_off,
  * the next one reads none below N0 + n - (K - 1).  trunet_resample_stream: a workgroup per tile, reads hist only.
  * trunet_resample_stream_commit, after it on the same stream: a workgroup per session, hist[slot] <- the last K - 1 samples
  * of [hist[slot] | packet] (zeros left of sample 0).  TRUNET_EINVAL without a launch for anything the host can see; a record
- * whose slot, packet, outputs or tiles lie outside slots, n_in, n_out or n_tiles is skipped by both kernels. */
+ * whose slot, packet, outputs or tiles lie outside slots, n_in, n_out or n_tiles is skipped by both kernels.
+ * All three entry points are resample.hip, and both tile kernels run its one tile function; resample.py lays its calls out
+ * by the limits below (tests/test_resample_cpu.py compares the two). */
+#define TRUNET_RS_MAX_TILE 4096             /* outputs per workgroup, at most */
+#define TRUNET_RS_SPAN_MAX 4608             /* floats of input a workgroup stages per window */
+#define TRUNET_RS_TAPS_LDS_MAX 16384        /* floats of the tap table that may live in LDS */
 #define TRUNET_RS_STREAM_INTS 10
 #define TRUNET_RS_STREAM_MAX_HISTORY 20480
 int trunet_resample_stream(const float* hist, const float* in, float* out, const int64_t* plan, const float* table, int half,

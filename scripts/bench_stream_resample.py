@@ -1,5 +1,5 @@
 """Cost of a stream pool at 48 and 44.1 kHz (tinyrecurrentunet_amd/streaming.py: StreamPool(fs=); resample.py:
-StreamResampler, resample_stream.hip) on one MI355X; prints one JSON line.
+StreamResampler, resample.hip) on one MI355X; prints one JSON line.
 
 Device events around a call, median of --reps after a warm-up, as bench_resample.py does it (DESIGN section 3m quotes them):
 

@@ -3,6 +3,7 @@ against scipy, the filter's response, the ratio arithmetic, the phase-major tap 
 point's refusals and every host-side refusal of resample / enhance(fs=...) / the dataset, and the command line's help."""
 import math
 import os
+import re
 import subprocess
 import sys
 
@@ -82,6 +83,11 @@ def test_phase_table_and_tiles():
     # every ratio the resampler accepts: the tile is a multiple of 256 and what a workgroup stages fits the declared budget;
     # a span that does not fit one window is staged in several (only for ratios far below 1)
     assert R.LDS_BUDGET <= 160 * 1024 and R.SPAN_FLOATS % 4 == 0
+    # the limits the module lays its calls out by are the ones the kernels are built with
+    with open(os.path.join(ROOT, "include", "trunet_hip.h")) as f:
+        defines = {k: int(v) for k, v in re.findall(r"^#define TRUNET_RS_(\w+) (\d+)\b", f.read(), re.M)}
+    assert defines == dict(MAX_TILE=R.MAX_TILE, SPAN_MAX=R.SPAN_FLOATS, TAPS_LDS_MAX=R.TAPS_LDS_FLOATS,
+                           STREAM_INTS=R.STREAM_INTS, STREAM_MAX_HISTORY=R.MAX_HISTORY)
     for p in range(1, R.MAX_RATIO + 1):
         for q in range(1, R.MAX_RATIO + 1):
             if math.gcd(p, q) != 1 or p == q:

@@ -1,4 +1,4 @@
-"""GPU: the stateful resampler (tinyrecurrentunet_amd/resample.py: StreamResampler, resample_stream.hip)
+"""GPU: the stateful resampler (tinyrecurrentunet_amd/resample.py: StreamResampler, resample.hip)
 and the stream pool at other rates than 16 kHz (streaming.py: StreamPool(fs=)).  The yardstick is bit-exactness: however a
 session is cut into packets, what feed and close returned is torch.equal to the offline resampler on the whole."""
 import numpy as np

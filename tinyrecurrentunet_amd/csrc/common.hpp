@@ -25,6 +25,17 @@ int trunet_launch_wgrad_small(const trunet_wgrad_args* h, hipStream_t st);
 // wgrad_small.hip: fused backward of a pointwise layer with <= 8 output rows (same contract as trunet_pw_bwd)
 int trunet_launch_pw_bwd_small(const trunet_pwbwd_args* H, hipStream_t st);
 
+// largest b in [0, n) with off[b * stride] <= v (a non-decreasing column of device prefix offsets, so an empty utterance
+// yields to the next).  Any b in [0, n) for a corrupt table: the caller validates what it gets.
+__device__ __forceinline__ int prefix_find(const int64_t* __restrict__ off, int n, int64_t v, int stride = 1) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[(size_t)mid * stride] <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // sum over the 32 lanes that share (lane >> 5)
 __device__ __forceinline__ float half_wave_sum(float v) {
     v += __shfl_xor(v, 16);

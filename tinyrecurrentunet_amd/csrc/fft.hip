@@ -1534,16 +1534,6 @@ __global__ void phm_bwd_kernel(const float2* __restrict__ m, const float2* __res
 // totals, or are not consistent with each other, is skipped, so no index derived from them leaves the buffers.
 struct RaggedUtt { int64_t s0, f0; int L, T; };
 
-// largest b in [0, B) with off[b] <= v (off non-decreasing); any b in [0, B) for a corrupt table
-__device__ __forceinline__ int ragged_find(const int64_t* __restrict__ off, int B, int64_t v) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ bool ragged_utt(const int64_t* __restrict__ so, const int64_t* __restrict__ fo, int b,
                                            int64_t nS, int64_t nT, RaggedUtt& u) {
     const int64_t s0 = so[b], s1 = so[b + 1], f0 = fo[b], f1 = fo[b + 1];
@@ -1557,7 +1547,7 @@ __device__ __forceinline__ bool ragged_utt(const int64_t* __restrict__ so, const
 __device__ __forceinline__ bool ragged_pair(const int64_t* __restrict__ so, const int64_t* __restrict__ fo,
                                             const int64_t* __restrict__ po, int B, int64_t nS, int64_t nT, int64_t p,
                                             RaggedUtt& u, int& t0) {
-    const int b = ragged_find(po, B, p);
+    const int b = prefix_find(po, B, p);
     if (!ragged_utt(so, fo, b, nS, nT, u)) return false;
     const int64_t p0 = po[b];
     if (p < p0 || po[b + 1] - p0 != (u.T + 1) / 2 || p - p0 >= (u.T + 1) / 2) return false;
@@ -1697,7 +1687,7 @@ __global__ __launch_bounds__(256) void ola_ragged_kernel(const float* __restrict
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= nS) return;
     RaggedUtt u;
-    const int b = ragged_find(so, B, g);
+    const int b = prefix_find(so, B, g);
     if (!ragged_utt(so, fo, b, nS, nT, u) || g < u.s0) return;
     const int j = (int)(g - u.s0);
     if (j >= u.L) return;

@@ -22,17 +22,6 @@ constexpr int SDR_CHUNK = 16384; // samples per workgroup of si_sdr_partials_ker
 constexpr int MAX_HALF_TAPS = 4096;
 constexpr double DEPS = 2.220446049250313e-16;   // np.finfo(np.float64).eps
 
-// largest b in [0, B) with off[b] <= v (off non-decreasing, so an empty utterance yields to the next); fft.hip's
-// ragged_find.  Any b in [0, B) for a corrupt table: the caller validates what it gets.
-__device__ __forceinline__ int utt_find(const int64_t* __restrict__ off, int B, int64_t v) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -52,7 +41,7 @@ __global__ __launch_bounds__(256) void resample_poly_kernel(const float* __restr
     __syncthreads();
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= nOut) return;
-    const int b = utt_find(oo, B, g);
+    const int b = prefix_find(oo, B, g);
     const int64_t i0 = io[b], i1 = io[b + 1], o0 = oo[b], o1 = oo[b + 1];
     if (i0 < 0 || i1 > nIn || i1 < i0 || o0 < 0 || o1 > nOut || o1 - o0 != ((i1 - i0) * p + q - 1) / q) return;
     if (g < o0 || g >= o1) return;
@@ -109,7 +98,7 @@ __global__ __launch_bounds__(256) void stoi_energy_kernel(StoiArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= a.nF) return;                                    // uniform over the wave
-    const int b = utt_find(a.fo, a.B, g);
+    const int b = prefix_find(a.fo, a.B, g);
     StoiUtt u;
     if (!stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) || g < u.f0 || g >= u.f0 + u.F) return;
     const float* x = a.sig + u.s0 + (g - u.f0) * SHOP;
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256) void stoi_bands_kernel(StoiArgs a, const cpx* 
     __shared__ float pw[2][SBINS + 3];
     const int tid = threadIdx.x;
     const int64_t g = blockIdx.x;
-    const int b = utt_find(a.fo, a.B, g);
+    const int b = prefix_find(a.fo, a.B, g);
     StoiUtt u;
     if (!stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) || g < u.f0 || g >= u.f0 + u.F) return;
     const int K = min(a.count[b], u.F);
@@ -224,7 +213,7 @@ __global__ __launch_bounds__(256) void stoi_segments_kernel(StoiArgs a) {
     __shared__ float tb[2][SEG_WG + NSEG - 1][NBAND];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t c = blockIdx.x;
-    const int b = utt_find(a.co, a.B, c);
+    const int b = prefix_find(a.co, a.B, c);
     StoiUtt u;
     if (!stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) || c < u.c0) return;
     const int nseg = min(a.count[b], u.F) - NSEG;             // K_b - 30 segments, when K_b - 1 >= 30
@@ -346,7 +335,7 @@ __global__ __launch_bounds__(256) void si_sdr_partials_kernel(const float* __res
                                                               int64_t nC) {
     __shared__ double red[256];
     const int64_t c = blockIdx.x;
-    const int b = utt_find(co, B, c);
+    const int b = prefix_find(co, B, c);
     const int64_t s0 = so[b], s1 = so[b + 1], c0 = co[b];
     if (s0 < 0 || s1 > nS || s1 < s0 || c0 < 0 || co[b + 1] > nC || co[b + 1] - c0 != (s1 - s0 + SDR_CHUNK - 1) / SDR_CHUNK)
         return;

@@ -31,7 +31,8 @@ from .enhance import _inputs
 
 MAX_RATIO = 640              # 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2, 96 kHz <-> 16 kHz; worst 11.025 -> 16: 640/441
 ZEROS, BETA, ROLLOFF = 16, 8.6, 0.94
-# resample.hip: RS_MAX_TILE, RS_SPAN_MAX (floats of input staged per window), RS_TAPS_LDS_MAX (floats of the tap table)
+# trunet_hip.h: TRUNET_RS_MAX_TILE, TRUNET_RS_SPAN_MAX (floats of input staged per window), TRUNET_RS_TAPS_LDS_MAX (floats of
+# the tap table); tests/test_resample_cpu.py compares them with the header
 MAX_TILE = 4096
 SPAN_FLOATS = 4608
 TAPS_LDS_FLOATS = 16384
@@ -75,6 +76,11 @@ def taps_per_output(p, half):
     return -(-(2 * half + 1) // p)
 
 
+def padded_taps(p, half):
+    """Kp: K rounded up to a multiple of 4, the floats of one row of the phase table"""
+    return (taps_per_output(p, half) + 3) & ~3
+
+
 def phase_table(h, p):
     """taps -> (p, Kp) phase-major table, table[r, k] = h[r + k p], zero past the last tap; Kp = K rounded up to 4"""
     h = np.asarray(h)
@@ -88,15 +94,14 @@ def phase_table(h, p):
 def span_floats(p, q, tile, half=None):
     """input samples the outputs of one full tile read, as resample.hip lays them out (a multiple of 4)"""
     half = ZEROS * max(p, q) if half is None else half
-    Kp = (taps_per_output(p, half) + 3) & ~3
-    return (((tile - 1) * q + p - 1) // p + Kp + 1 + 3) & ~3
+    return (((tile - 1) * q + p - 1) // p + padded_taps(p, half) + 1 + 3) & ~3
 
 
 def tile_outputs(p, q, half=None):
     """outputs per workgroup: the largest multiple of 256, at most MAX_TILE, whose input span fits SPAN_FLOATS.  Ratios far
     below 1 (q / p above 16 or so) do not fit even at 256; the kernel then stages the span in windows of SPAN_FLOATS."""
     half = ZEROS * max(p, q) if half is None else half
-    room = SPAN_FLOATS - ((taps_per_output(p, half) + 3) & ~3) - 1      # ceil((tile - 1) q / p) must fit it
+    room = SPAN_FLOATS - padded_taps(p, half) - 1       # ceil((tile - 1) q / p) must fit it
     return min(max((room * p // q + 1) // 256 * 256, 256), MAX_TILE)
 
 
@@ -107,14 +112,14 @@ def windows(p, q, half=None):
 
 def taps_in_lds(p, half):
     """whether the kernel keeps the tap table in LDS (it must fit TAPS_LDS_FLOATS) or reads its rows from L2"""
-    return p * ((taps_per_output(p, half) + 3) & ~3) <= TAPS_LDS_FLOATS
+    return p * padded_taps(p, half) <= TAPS_LDS_FLOATS
 
 
 def lds_bytes(p, q, half=None):
     """LDS one workgroup asks for"""
     half = ZEROS * max(p, q) if half is None else half
     span = min(span_floats(p, q, tile_outputs(p, q, half), half), SPAN_FLOATS)
-    return 4 * (span + (p * ((taps_per_output(p, half) + 3) & ~3) if taps_in_lds(p, half) else 0))
+    return 4 * (span + (p * padded_taps(p, half) if taps_in_lds(p, half) else 0))
 
 
 def plan(lens, p, q, tile):
@@ -134,6 +139,25 @@ def plan(lens, p, q, tile):
     return outs, offs
 
 
+def _filter(p, q, taps=None):
+    """What both resamplers derive from a ratio, host only -> (float64 taps: ``design``'s, or ``taps``, 2 half + 1 of them
+    with half a multiple of max(p, q); half; K; outputs per tile; whether the tap table fits LDS)"""
+    if taps is None:
+        h, half = design(p, q)
+    else:
+        h = np.asarray(taps, dtype=np.float64)
+        half = (h.shape[0] - 1) // 2
+        big = max(p, q)
+        if h.ndim != 1 or h.shape[0] != 2 * half + 1 or half < big or half % big:
+            raise ValueError("taps: 2 half + 1 values with half a positive multiple of max(p, q) = %d" % big)
+    return h, half, taps_per_output(p, half), tile_outputs(p, q, half), taps_in_lds(p, half)
+
+
+def _upload(h, p, device):
+    """taps -> the fp32 phase table on the device"""
+    return torch.from_numpy(phase_table(h, p).astype(np.float32)).to(device).contiguous()
+
+
 class Resampler:
     """fs_in -> fs_out with the device copy of the tap table and the layout constants kept for repeated calls.
     ``taps``: other taps than ``design``'s (float64, 2 half + 1 of them, half a multiple of max(p, q));
@@ -149,21 +173,12 @@ class Resampler:
         self._rows = {}
         if self.identity:
             return
-        if taps is None:
-            h, self.half = design(self.p, self.q)
-        else:
-            h = np.asarray(taps, dtype=np.float64)
-            self.half = (h.shape[0] - 1) // 2
-            big = max(self.p, self.q)
-            if h.ndim != 1 or h.shape[0] != 2 * self.half + 1 or self.half < big or self.half % big:
-                raise ValueError("taps: 2 half + 1 values with half a positive multiple of max(p, q) = %d" % big)
-        self.K = taps_per_output(self.p, self.half)
-        self.tile = tile_outputs(self.p, self.q, self.half)
-        self.lds_taps = taps_in_lds(self.p, self.half) if lds_taps is None else bool(lds_taps)
-        if self.lds_taps and not taps_in_lds(self.p, self.half):
+        h, self.half, self.K, self.tile, fits = _filter(self.p, self.q, taps)
+        self.lds_taps = fits if lds_taps is None else bool(lds_taps)
+        if self.lds_taps and not fits:
             raise ValueError("a table of %d x %d taps does not fit the LDS share of %d floats"
-                             % (self.p, (self.K + 3) & ~3, TAPS_LDS_FLOATS))
-        self.table = torch.from_numpy(phase_table(h, self.p).astype(np.float32)).to(self.device).contiguous()
+                             % (self.p, padded_taps(self.p, self.half), TAPS_LDS_FLOATS))
+        self.table = _upload(h, self.p, self.device)
 
     def out_lengths(self, lens):
         return [out_length(n, self.p, self.q) for n in lens]
@@ -396,8 +411,8 @@ class StreamResampler:
 
     However a session x of N samples is cut -- empty packets, single samples, everything at once -- the concatenation of
     what ``feed`` returned for it and what ``close`` returns is bit for bit ``resample([x], fs_in, fs_out)[0]``,
-    ceil(N p / q) samples: the kernels (resample_stream.hip) evaluate ``resample_rational_kernel``'s per-output expression
-    on the line [the slot's last K - 1 samples | the packet].  After N samples ``ready(N)`` outputs are out; the rest wait
+    ceil(N p / q) samples: both kernels run resample.hip's one tile function, the streaming one on the line [the slot's
+    last K - 1 samples | the packet].  After N samples ``ready(N)`` outputs are out; the rest wait
     for half / p more samples (16 at the lower of the two rates) or for ``close``, which supplies zeros.  ``history``
     derives why K - 1 samples per slot are all the state; the sample and output counts are host integers, and a slot
     whose count is zero reads nothing of its history, so ``reset`` / ``close`` are host work.  One call is one launch of
@@ -424,20 +439,17 @@ class StreamResampler:
         if self.identity:
             self.half = self.K = self.H = 0
             return
-        self._h, self.half = design(self.p, self.q)
-        self.K = taps_per_output(self.p, self.half)
+        self._h, self.half, self.K, self.tile, self.lds_taps = _filter(self.p, self.q)
         self.H = history(self.p, self.half)
         if self.H > MAX_HISTORY:
             raise ValueError("%d -> %d Hz keeps %d samples per session, and a stream keeps at most %d"
                              % (self.fs_in, self.fs_out, self.H, MAX_HISTORY))
-        self.tile = tile_outputs(self.p, self.q, self.half)
-        self.lds_taps = taps_in_lds(self.p, self.half)
 
     # ---- device state, made with the first call that needs it
     @property
     def table(self):
         if self._table is None:
-            self._table = torch.from_numpy(phase_table(self._h, self.p).astype(np.float32)).to(self.device).contiguous()
+            self._table = _upload(self._h, self.p, self.device)
         return self._table
 
     @property
