@@ -11,10 +11,10 @@
 //
 // Decomposition: a tile is (source position q, 32 frames).  A workgroup owns whole frame chunks and walks q = 0 .. Lin-1,
 // so the dz rows p = q S - pad .. q S - pad + K - 1 form a sliding window: every dz row is loaded and BatchNorm-transformed
-// ONCE per chunk into a ring of K + 2 S row sets and serves all K taps (positions) that need it; every step brings S new dz
+// ONCE per chunk into a ring of K + LA S row sets and serves all K taps (positions) that need it; every step brings S new dz
 // rows (dy into the ring, z into a staging slot, combined in place by the thread that requested the piece) and one source
-// row set.  LDS-DMA (global_load_lds) two steps ahead, counted vmcnt, one barrier per step, 16-byte pieces XOR-swizzled
-// through the source address as in conv_wgrad_kernel / pw_bwd_kernel.
+// row set.  LDS-DMA (global_load_lds) LA steps ahead (CtLds::LA: two, one in the stride-2 split instances), counted vmcnt,
+// one barrier per step, 16-byte pieces XOR-swizzled through the source address as in conv_wgrad_kernel / pw_bwd_kernel.
 //
 // All 8 waves carry the same MFMA load (16 K per step, two waves per SIMD):
 //   waves 0-3  loaders + weight gradient: wave (ci tile, co tile) keeps its K accumulators (one per tap) for the whole
@@ -29,13 +29,13 @@
 // fp32-grade result, one workgroup per CU).  Decomposition, rings, DMA schedule, prologue arithmetic and epilogue are the
 // same text; what differs is how a staged fp32 fragment reaches the matrix pipe:
 //   weight gradient (waves 0-3): per 16 frames the source row's 8 values of a lane (two swizzled 16-byte pieces) get
-//       BatchNorm+ReLU and are split ONCE, every valid tap's dz row fragment is split, 6 v_mfma_f32_32x32x16_bf16 per tap;
+//       BatchNorm+ReLU and are split ONCE, every valid tap's dz row fragment comes as planes, 6 v_mfma_f32_32x32x16_bf16 per tap;
 //   data gradient (waves 4-7): W^T of the wave's (ci tile, co half) for all taps sits in registers as three bf16 fragment
-//       planes (split once per kernel), per tap and 16 co rows the lane's 8 dz values (8 ds_read_b32) are split, 6 MFMAs.
-// Here a staged fragment feeds ONE 32-row tile per wave, so the split is not amortised (about 7 vector instructions per
-// MFMA: the waves are vector-bound) -- and still well ahead of the fp32 MFMA: 6 x 33 matrix cycles + ~45 x 4 vector cycles
-// per (32 x 32 x 16) against 8 x 64.  The fp32-MFMA instance was the most matrix-bound kernel of the step (matrix pipe
-// 62-65 % busy, HBM at 0.25 of its peak).
+//       planes (split once per kernel), per tap and 16 co rows the lane's dz planes come through transposing reads, 6 MFMAs.
+// Here a staged fragment feeds ONE 32-row tile per wave, so a split by the consuming wave is not amortised (about 7 vector
+// instructions per MFMA: such waves are vector-bound; still well ahead of the fp32 MFMA, 6 x 33 matrix cycles + ~45 x 4
+// vector cycles per (32 x 32 x 16) against 8 x 64) -- hence the dz planes below.  The fp32-MFMA instance was the most
+// matrix-bound kernel of the step (matrix pipe 62-65 % busy, HBM at 0.25 of its peak).
 #include <type_traits>
 #include "dma_common.hpp"
 #include "x3_common.hpp"
@@ -48,13 +48,16 @@ constexpr int CT_SET = CT_C * CT_F; // floats per row set (8 KB)
 constexpr int CT_GRID = TRUNET_NUM_CU;
 constexpr int CT_LO = CT_C * 16;    // floats per row set of the lo-plane ring (8 bytes per 4 frames)
 
-// (X3; round 4, as in pw_bwd.hip) dz is split ONCE, by the prologue pass that computes it: the dz ring keeps [hi | mid] of a
-// piece's 4 frames in the piece's own 16 bytes, a second ring of 4 KB slots the lo plane.  The weight-gradient B fragments
+// (X3; as in pw_bwd.hip) dz is split ONCE, by the prologue pass that computes it: the dz ring keeps [hi | mid] of a piece's
+// 4 frames in the piece's own 16 bytes, a second ring of 4 KB slots the lo plane.  The weight-gradient B fragments
 // (K = frames) are then 8-byte reads, the data-gradient B fragments (K = dz rows) transposing reads (ds_read_b64_tr_b16),
-// neither with vector work; only the source rows are still split by the wave that consumes them.  Needs (K + 2 S) x 4 KB
-// more LDS: k3 s1 fits (126 KB); k3 s2 (166 KB) and k5 s2 (190 KB) do not and keep the consumer-side split.
-template <int K, int S>
-constexpr bool ct_dzp() { return K == 3 && S == 1; }
+// neither with vector work; only the source rows are still split by the wave that consumes them.  Needs RDZ x 4 KB more
+// LDS.  With two steps of DMA lead (RDZ = K + 2 S, 2 S staging slots, 4 source slots) k3 s1 fits (126 KB); k3 s2 (166 KB)
+// and k5 s2 (190 KB) do not, so the stride-2 split instances run with ONE step of lead (ct_lookahead): RDZ = K + S, S
+// staging slots, 3 source slots -- k3 s2 118 KB, k5 s2 142 KB.  A step of k5 s2 lasts several microseconds: the rows of
+// step q + 2 are requested behind the barrier that ends step q and awaited behind the last K-step of step q + 1.
+template <int K, int S, bool X3>
+constexpr int ct_lookahead() { return X3 && S == 2 ? 1 : 2; }
 
 // float offset of the 8 lo bytes of logical piece `pc` of row `r` inside a lo-ring slot (same swizzle as the row set)
 __device__ __forceinline__ int ct_lo_off(int r, int pc) { return r * 16 + 2 * (pc ^ ((r >> 1) & 7)); }
@@ -66,10 +69,12 @@ __device__ __forceinline__ void ct_bstore(__amdgpu_buffer_rsrc_t r, int voff, in
 // ring depths and the carve-up of the dynamic LDS (float offsets), for the kernel and its launcher
 template <int K, int S, bool X3>
 struct CtLds {
-    static constexpr bool DZP = X3 && ct_dzp<K, S>();
-    static constexpr int RDZ = K + 2 * S;       // dz ring: window + the rows of the next two steps
-    static constexpr int ZS = 2 * S;            // z staging slots
-    static constexpr int RS = 4;                // source ring: q (+ epilogue of q - 1), q + 1, q + 2
+    static constexpr bool DZP = X3;
+    static constexpr int LA = ct_lookahead<K, S, X3>();     // DMA lead in steps: behind the barrier of step q go the rows of step q + 1 + LA
+    static_assert(LA == 1 || LA == 2, "the counted wait of the step loop leaves at most one issue in flight");
+    static constexpr int RDZ = K + LA * S;      // dz ring: window + the rows of the next LA steps
+    static constexpr int ZS = LA * S;           // z staging slots: the rows not yet transformed
+    static constexpr int RS = LA + 2;           // source ring: q - 1 (its epilogue runs during step q), q .. q + LA
     static constexpr int DZ = 0;                                // [RDZ][64][32]
     static constexpr int ZST = DZ + RDZ * CT_SET;               // [ZS][64][32]
     static constexpr int SRC = ZST + ZS * CT_SET;               // [RS][64][32]
@@ -89,7 +94,7 @@ struct CtWtX3 { u32x4 A0[K][2], A1[K][2], A2[K][2]; };  // planes of co = 32 chf
 template <int K, int S, bool X3>
 __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet_convt_bwd_args a) {
     using L = CtLds<K, S, X3>;
-    constexpr int PAD = S / 2, RDZ = L::RDZ, ZS = L::ZS, RS = L::RS;
+    constexpr int PAD = S / 2, RDZ = L::RDZ, ZS = L::ZS, RS = L::RS, LA = L::LA;
     constexpr bool DZP = L::DZP;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* DZ = smem + L::DZ;
@@ -110,6 +115,13 @@ __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet
         CA[r] = f32x4{a.ca[r], a.cb[r], a.cc[r], 0.f};
         CB[r] = f32x4{a.s_scale[r], a.s_shift[r], a.s_mean[r], 0.f};
     }
+    // ring slot of dz row p for the fragment reads.  The stride-2 split instances pass it through an SGPR the compiler does
+    // not see through: it otherwise folds the slot arithmetic into one lane address per (tap, read) -- about 40 VGPRs of
+    // address constants in k5 s2, which then spills its W^T fragments
+    auto dz_slot = [](int p) __attribute__((always_inline)) {
+        if constexpr (X3 && S == 2) return wave_uniform(p % RDZ);
+        else return p % RDZ;
+    };
     const int nfc = NP / CT_F;
     const int c_begin = (int)(((long long)blockIdx.x * nfc) / gridDim.x);
     const int c_end = (int)(((long long)(blockIdx.x + 1) * nfc) / gridDim.x);
@@ -195,24 +207,27 @@ __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet
         auto new_lo = [&](int q) { return q * S - PAD + K - S; };
 
         // K-steps of a position (the fp32 MFMA takes 8 frames, the six bf16 MFMAs 16) and the one that carries the
-        // prologue of the next position
-        constexpr int NQQ = X3 ? CT_F / 16 : CT_F / 8, QQ_PRO = X3 ? 0 : 1;
+        // prologue of the next position.  With one step of lead that is the last one: the rows were requested behind the
+        // barrier that opened this step, and the wait in front of the prologue is the only place where the wave can stand
+        // for them (k5 s2: 1.88 ms per step against 1.96 ms with the prologue behind the first K-step, profiles/ctb2_a)
+        constexpr int NQQ = X3 ? CT_F / 16 : CT_F / 8, QQ_PRO = X3 ? (LA == 1 ? NQQ - 1 : 0) : 1;
 
         for (int ch = c_begin; ch < c_end; ++ch) {
             const int n0 = ch * CT_F;
-            // ---- run start: the window of step 0 and the rows of step 1, ZS rows at a time (the z staging area holds ZS
-            // row sets), sources 0 and 1; then the rows of step 2 go in flight
+            // ---- run start: the window of step 0 and the rows of the steps below LA, ZS rows at a time (the z staging area
+            // holds ZS row sets), sources 0 .. LA - 1 (LA <= 2: source 1 rides with the second batch of rows, or alone when
+            // there is none); then the rows of step LA go in flight
             {
-                const int pa = -PAD, pb = new_lo(1) + S;            // rows of steps 0 and 1
+                const int pa = -PAD, pb = new_lo(LA - 1) + S;       // rows of steps 0 .. LA - 1
                 for (int p = pa; p < pb; p += ZS) {
-                    issue(p, min(p + ZS, pb), p == pa ? 0 : (p == pa + ZS ? 1 : -1), n0);
+                    issue(p, min(p + ZS, pb), p == pa ? 0 : (LA == 2 && p == pa + ZS ? 1 : -1), n0);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     prologue(p, min(p + ZS, pb), n0);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
-                if (pb - pa <= ZS) { issue(0, 0, 1, n0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+                if (LA == 2 && pb - pa <= ZS) { issue(0, 0, 1, n0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
             }
-            int n_last = issue(new_lo(2), new_lo(2) + S, 2, n0);        // rows of step 2 (only when Lin > 2)
+            int n_last = issue(new_lo(LA), new_lo(LA) + S, LA, n0);     // rows of step LA (only when Lin > LA)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -236,22 +251,16 @@ __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet
                         for (int k = 0; k < K; ++k) {
                             const int p = q * S - PAD + k;
                             if (p >= 0 && p < Lout) {
-                                const float* Dp = DZ + (p % RDZ) * CT_SET;
-                                u32x4 b0, b1, b2;
-                                if constexpr (DZP) {
-                                    const float* Lp = LO + (p % RDZ) * CT_LO;
-                                    const u32x4 q0 = *(const u32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h));
-                                    const u32x4 q1 = *(const u32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h + 1));
-                                    const u32x2 l0 = *(const u32x2*)(Lp + ct_lo_off(rb, 4 * qq + 2 * h));
-                                    const u32x2 l1 = *(const u32x2*)(Lp + ct_lo_off(rb, 4 * qq + 2 * h + 1));
-                                    b0 = u32x4{q0[0], q0[1], q1[0], q1[1]};
-                                    b1 = u32x4{q0[2], q0[3], q1[2], q1[3]};
-                                    b2 = u32x4{l0[0], l0[1], l1[0], l1[1]};
-                                } else {
-                                    const f32x4 bv0 = *(const f32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h));
-                                    const f32x4 bv1 = *(const f32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h + 1));
-                                    ctx_split8(bv0, bv1, b0, b1, b2);
-                                }
+                                const int sl = dz_slot(p);
+                                // the dz planes as the prologue left them: [hi | mid] in the piece, lo in the lo ring
+                                const float* Dp = DZ + sl * CT_SET;
+                                const float* Lp = LO + sl * CT_LO;
+                                const u32x4 q0 = *(const u32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h));
+                                const u32x4 q1 = *(const u32x4*)(Dp + swz_off(rb, 4 * qq + 2 * h + 1));
+                                const u32x2 l0 = *(const u32x2*)(Lp + ct_lo_off(rb, 4 * qq + 2 * h));
+                                const u32x2 l1 = *(const u32x2*)(Lp + ct_lo_off(rb, 4 * qq + 2 * h + 1));
+                                const u32x4 b0 = {q0[0], q0[1], q1[0], q1[1]}, b1 = {q0[2], q0[3], q1[2], q1[3]},
+                                            b2 = {l0[0], l0[1], l1[0], l1[1]};
                                 CTX_MF6(acc[k], a0, a1, a2, b0, b1, b2);
                             }
                         }
@@ -270,18 +279,18 @@ __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet
                             }
                         }
                     }
-                    if (qq == QQ_PRO && q >= 1) {
-                        // outstanding: rows of step q + 1 (older) and of step q + 2 (the newest n_last): transform the
-                        // rows of step q + 1 in the shadow of this step's MFMAs
-                        wait_vmcnt_exact<31>(n_last);
+                    if (qq == QQ_PRO && q >= LA - 1) {
+                        // outstanding: the rows of step q + 1 (oldest) and, with LA = 2, of step q + 2 (the newest n_last):
+                        // transform the rows of step q + 1 in the shadow of this step's MFMAs
+                        wait_vmcnt_exact<31>(LA == 2 ? n_last : 0);
                         prologue(new_lo(q + 1), new_lo(q + 1) + S, n0);
                     }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();            // every LDS read of step q is done; step q + 1 is staged
                 asm volatile("" ::: "memory");
-                // free now: the ring slots of the rows that left the window, S staging slots, source slot (q + 3) % RS
-                n_last = (q + 3 < Lin) ? issue(new_lo(q + 3), new_lo(q + 3) + S, q + 3, n0) : 0;
+                // free now: the ring slots of the rows that left the window, S staging slots, source slot (q + 1 + LA) % RS
+                n_last = (q + 1 + LA < Lin) ? issue(new_lo(q + 1 + LA), new_lo(q + 1 + LA) + S, q + 1 + LA, n0) : 0;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                // the rings are reused by the next chunk
@@ -381,8 +390,9 @@ __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet
                     if constexpr (DZP) {
                         // K-step ks: lane (G = lane >> 4, i = lane & 15) fetches the 4 frames of logical piece 4 (G & 1) + (i & 3) of row
                         // 32 chf + 16 ks + 8 h + 4 t + (i >> 2) and receives frame c of the rows 8 h + 4 t .. + 3 (t = 0, 1)
-                        const float* Dq = DZ + (p % RDZ) * CT_SET;
-                        const float* Lq = LO + (p % RDZ) * CT_LO;
+                        const int sl = dz_slot(p);
+                        const float* Dq = DZ + sl * CT_SET;
+                        const float* Lq = LO + sl * CT_LO;
 #pragma unroll
                         for (int ks = 0; ks < 2; ++ks) {
                             const int r0 = chf * 32 + 16 * ks + trr;
@@ -391,23 +401,6 @@ __global__ __launch_bounds__(512, X3 ? 1 : 2) void convt_bwd_kernel(const trunet
                             const u32x2 l0 = lds_tr16(Lq + ct_lo_off(r0, trp)), l1 = lds_tr16(Lq + ct_lo_off(r0 + 4, trp));
                             const u32x4 b0 = {h0[0], h0[1], h1[0], h1[1]}, b1 = {m0[0], m0[1], m1[0], m1[1]},
                                         b2 = {l0[0], l0[1], l1[0], l1[1]};
-                            CTX_MF6(dacc, wt.A0[k][ks], wt.A1[k][ks], wt.A2[k][ks], b0, b1, b2);
-                        }
-                    } else if constexpr (X3) {
-                        // K-step ks: dz rows 32 chf + 16 ks + 8 h + j (j < 8), swizzle term (4 h + (j >> 1)) & 7 (32 chf + 16 ks
-                        // is a multiple of 16)
-                        const float* Sb = DZ + (p % RDZ) * CT_SET + (chf * 32 + 8 * h) * CT_F + (c & 3);
-                        const int cpc = c >> 2;
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks) {
-                            f32x4 x0, x1;
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                x0[j] = Sb[(16 * ks + j) * CT_F + 4 * (cpc ^ ((4 * h + (j >> 1)) & 7))];
-                                x1[j] = Sb[(16 * ks + 4 + j) * CT_F + 4 * (cpc ^ ((4 * h + 2 + (j >> 1)) & 7))];
-                            }
-                            u32x4 b0, b1, b2;
-                            ctx_split8(x0, x1, b0, b1, b2);
                             CTX_MF6(dacc, wt.A0[k][ks], wt.A1[k][ks], wt.A2[k][ks], b0, b1, b2);
                         }
                     } else {
