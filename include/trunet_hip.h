@@ -246,7 +246,7 @@ int trunet_conv_first_fwd(const float* x, const float* w, const float* b, float*
 /* (its weight gradient is trunet_conv_wgrad with one segment per tap, pos_mul = stride) */
 
 /* Depthwise Conv1d (network.py:33-38, groups=C, padding=k/2) with BN+ReLU prologue on the input and
- * statistics of the raw output: partials [nparts][C][2]. */
+ * statistics of the raw output: partials [nparts][C][2].  (csrc/depthwise.hip, with the bf16 entry points below) */
 int trunet_dwconv_fwd(const float* zin, const float* s_in, const float* t_in, const float* w,
                       const float* b, float* zout, float* partials, int C, int K, int S, int Lin, int Lout,
                       int NP, int N, void* stream);
@@ -823,7 +823,7 @@ typedef struct {
 } trunet_bconvt_args;
 int trunet_bf16_convt_bwd_nparts(void);
 int trunet_bf16_convt_bwd(const trunet_bconvt_args* h_args, void* stream);
-/* depthwise conv in the octet layout (network.py:33-38): BN+ReLU prologue on the input, raw bf16 output, fp32 statistics
+/* depthwise conv in the octet layout (network.py:33-38; csrc/depthwise.hip): BN+ReLU prologue on the input, raw bf16 output, fp32 statistics
  * partials[trunet_bf16_dw_nparts(NP, rows)][C][2] (rows = Lout forward, Lin backward); backward: dz = ca dy + cb z + cc, masked
  * data gradient of the input (+ its BatchNorm-backward sums), fp32 partial images w_partials[nparts][C][K],
  * b_partials[nparts][C].  A thread owns (octet, frame) and walks positions with a sliding register window: every tensor is

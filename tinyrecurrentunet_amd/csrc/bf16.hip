@@ -810,214 +810,6 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwgrad_kernel(const trunet_bwgr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// depthwise conv, octet layout.  A thread owns (octet = blockIdx.y, frame, chunk of positions = blockIdx.z) and walks the
-// positions with a sliding window in registers: every input row is loaded once.
-// every row is touched exactly once: non-temporal accesses (same-box A/B: -0.5 ms per step; -DTRUNET_DW_TEMPORAL builds the
-// default-policy form)
-#ifndef TRUNET_DW_TEMPORAL
-#define BDW_LD(p) __builtin_nontemporal_load((const u32x4*)(p))
-#define BDW_ST(p, v) __builtin_nontemporal_store((v), (u32x4*)(p))
-#else
-#define BDW_LD(p) (*(const u32x4*)(p))
-#define BDW_ST(p, v) (*(u32x4*)(p) = (v))
-#endif
-
-template <int NV>
-__device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* smem /* [4][NV] */, float* dst, int stride) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float s = wave_sum(v[i]);
-        if (lane == 0) smem[wave * NV + i] = s;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NV; i += 256)
-        dst[(size_t)i * stride] = (smem[i] + smem[NV + i]) + (smem[2 * NV + i] + smem[3 * NV + i]);
-    __syncthreads();
-}
-
-__host__ __device__ inline int bdw_chunks(int rows) { return rows >= 32 ? 4 : (rows >= 16 ? 2 : 1); }
-
-template <int K, int S>
-__global__ __launch_bounds__(256) void bdw_fwd_kernel(const u32x4* __restrict__ zin, const float* __restrict__ s_in,
-                                                      const float* __restrict__ t_in, const float* __restrict__ w,
-                                                      const float* __restrict__ b, u32x4* __restrict__ zout,
-                                                      float* __restrict__ partials, int C, int Lin, int Lout, int NP, int N) {
-    __shared__ float red[4 * 16];
-    const int oct = blockIdx.y;
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    const int nch = gridDim.z;
-    const int lo0 = (int)(((long long)blockIdx.z * Lout) / nch), lo1 = (int)(((long long)(blockIdx.z + 1) * Lout) / nch);
-    float sc[8], sh[8], bb[8], wk[8][K];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ch = oct * 8 + j;
-        sc[j] = s_in[ch]; sh[j] = t_in[ch]; bb[j] = b[ch];
-#pragma unroll
-        for (int k = 0; k < K; ++k) wk[j][k] = w[ch * K + k];
-    }
-    float st[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) st[j] = 0.f;
-    const u32x4* src = zin + (size_t)oct * Lin * NP + n;
-    u32x4* dst = zout + (size_t)oct * Lout * NP + n;
-    auto load_act = [&](int li, float (&act)[8]) {
-        if (li >= 0 && li < Lin) {
-            float v[8];
-            bf_unpack8(BDW_LD(src + (size_t)li * NP), v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) act[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), 0.f);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) act[j] = 0.f;
-        }
-    };
-    float win[K][8];                    // win[k] = activated input at li = lo*S + k - K/2
-#pragma unroll
-    for (int k = 0; k < K - S; ++k) load_act(lo0 * S + k - K / 2, win[k + S]);       // pre-shifted: the loop shifts first
-    for (int lo = lo0; lo < lo1; ++lo) {
-#pragma unroll
-        for (int k = 0; k < K - S; ++k)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) win[k][j] = win[k + S][j];
-#pragma unroll
-        for (int k = K - S; k < K; ++k) load_act(lo * S + k - K / 2, win[k]);
-        float acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            acc[j] = bb[j];
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc[j] = fmaf(wk[j][k], win[k][j], acc[j]);
-        }
-        const u32x4 o = bf_pack8(acc);
-        BDW_ST(dst + (size_t)lo * NP, o);
-        if (n < N) {
-            float r[8];
-            bf_unpack8(o, r);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { st[2 * j] += r[j]; st[2 * j + 1] = fmaf(r[j], r[j], st[2 * j + 1]); }
-        }
-    }
-    const int part = blockIdx.z * gridDim.x + blockIdx.x;
-    block_reduce_store<16>(st, red, partials + ((size_t)part * C + oct * 8) * 2, 1);
-}
-
-// backward: groups of S input positions li = m*S + e; the taps of a group touch the dz rows m + LOMIN .. m + LOMAX, which
-// are kept (BatchNorm-backward transformed) in a 3-row register window and advance by one row per group.
-template <int K, int S>
-__global__ __launch_bounds__(256) void bdw_bwd_kernel(const u32x4* __restrict__ dy, const u32x4* __restrict__ z,
-                                                      const float* __restrict__ ca, const float* __restrict__ cb,
-                                                      const float* __restrict__ cc, const u32x4* __restrict__ zin,
-                                                      const float* __restrict__ s_in, const float* __restrict__ t_in,
-                                                      const float* __restrict__ mean_in, const float* __restrict__ w,
-                                                      u32x4* __restrict__ dy_in, float* __restrict__ partials_in,
-                                                      float* __restrict__ w_partials, float* __restrict__ b_partials, int C,
-                                                      int Lin, int Lout, int NP, int N) {
-    constexpr int LOMIN = -1, LOMAX = 1, W = 3;
-    static_assert((K == 3 && S == 1) || (K == 5 && S == 2) || (K == 3 && S == 2), "window derived for these shapes");
-    __shared__ float red[4 * 8 * (K + 1)];
-    const int oct = blockIdx.y;
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    const int G = (Lin + S - 1) / S;
-    const int nch = gridDim.z;
-    const int m0 = (int)(((long long)blockIdx.z * G) / nch), m1 = (int)(((long long)(blockIdx.z + 1) * G) / nch);
-    float a0[8], a1[8], a2[8], sc[8], sh[8], mu[8], wk[8][K];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ch = oct * 8 + j;
-        a0[j] = ca[ch]; a1[j] = cb[ch]; a2[j] = cc[ch];
-        sc[j] = s_in[ch]; sh[j] = t_in[ch]; mu[j] = mean_in[ch];
-#pragma unroll
-        for (int k = 0; k < K; ++k) wk[j][k] = w[ch * K + k];
-    }
-    float st[16], dwb[8 * (K + 1)];       // dwb[j*(K+1) + k] = dw[j][k], [.. + K] = db[j]
-#pragma unroll
-    for (int j = 0; j < 16; ++j) st[j] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8 * (K + 1); ++j) dwb[j] = 0.f;
-    const u32x4* pdy = dy + (size_t)oct * Lout * NP + n;
-    const u32x4* pz = z + (size_t)oct * Lout * NP + n;
-    const u32x4* pin = zin + (size_t)oct * Lin * NP + n;
-    u32x4* pout = dy_in + (size_t)oct * Lin * NP + n;
-    const bool fin = n < N;
-    auto load_dz = [&](int lo, float (&d)[8]) {
-        if (lo >= 0 && lo < Lout && fin) {
-            float dv[8], zv[8];
-            bf_unpack8(BDW_LD(pdy + (size_t)lo * NP), dv);
-            bf_unpack8(BDW_LD(pz + (size_t)lo * NP), zv);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = fmaf(a0[j], dv[j], fmaf(a1[j], zv[j], a2[j]));
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = 0.f;
-        }
-    };
-    float dzw[W][8];                    // dzw[i] = dz row m + LOMIN + i
-#pragma unroll
-    for (int i = 1; i < W; ++i) load_dz(m0 + LOMIN + i - 1, dzw[i]);                 // pre-shifted
-    for (int m = m0; m < m1; ++m) {
-#pragma unroll
-        for (int i = 0; i < W - 1; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) dzw[i][j] = dzw[i + 1][j];
-        load_dz(m + LOMAX, dzw[W - 1]);
-#pragma unroll
-        for (int e = 0; e < S; ++e) {
-            const int li = m * S + e;
-            if (li >= Lin) continue;
-            float zi[8], act[8], g[8];
-            bf_unpack8(BDW_LD(pin + (size_t)li * NP), zi);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { act[j] = fmaxf(fmaf(zi[j], sc[j], sh[j]), 0.f); g[j] = 0.f; }
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                constexpr int half = K / 2;
-                const int num = e + half - k;                        // relative to m*S; compile-time after unrolling
-                if (((num % S) + S) % S != 0) continue;
-                const int lo_rel = (num >= 0) ? num / S : -((-num) / S);
-                const int wi = lo_rel - LOMIN;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float dzv = dzw[wi][j];
-                    g[j] = fmaf(wk[j][k], dzv, g[j]);
-                    dwb[j * (K + 1) + k] = fmaf(dzv, act[j], dwb[j * (K + 1) + k]);
-                    if (k == half) dwb[j * (K + 1) + K] += dzv;      // e == 0 here: every dz row counted once
-                }
-            }
-            float ov[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ov[j] = (act[j] > 0.f) ? g[j] : 0.f;
-            const u32x4 o = bf_pack8(ov);
-            BDW_ST(pout + (size_t)li * NP, o);
-            float r[8];
-            bf_unpack8(o, r);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { st[2 * j] += r[j]; st[2 * j + 1] = fmaf(r[j], zi[j] - mu[j], st[2 * j + 1]); }
-        }
-    }
-    const int part = blockIdx.z * gridDim.x + blockIdx.x;
-    block_reduce_store<16>(st, red, partials_in + ((size_t)part * C + oct * 8) * 2, 1);
-    // dw / db: [part][C][K] and [part][C]
-    {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int i = 0; i < 8 * (K + 1); ++i) {
-            const float s = wave_sum(dwb[i]);
-            if (lane == 0) red[wave * 8 * (K + 1) + i] = s;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < 8 * (K + 1); i += 256) {
-            const int NVV = 8 * (K + 1);
-            const float s = (red[i] + red[NVV + i]) + (red[2 * NVV + i] + red[3 * NVV + i]);
-            const int j = i / (K + 1), k = i - j * (K + 1);
-            const int ch = oct * 8 + j;
-            if (k < K) w_partials[((size_t)part * C + ch) * K + k] = s;
-            else b_partials[(size_t)part * C + ch] = s;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // layout changes: fp32 frames-last [C][R] (R = L*NP) <-> bf16 octets [C/8][R][8]
 __global__ void from_fl_kernel(const float* __restrict__ x, u32x4* __restrict__ y, int C, size_t R) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;      // (oct, r)
@@ -1324,46 +1116,6 @@ extern "C" int trunet_bf16_pw_bwd(const trunet_bpwbwd_args* H, void* stream) {
     } while (0)
     if (bn) BWD_LAUNCH(TRUNET_PRO_BNRELU); else BWD_LAUNCH(TRUNET_PRO_NONE);
 #undef BWD_LAUNCH
-    return trunet_launch_status();
-}
-
-extern "C" int trunet_bf16_dw_nparts(int NP, int rows) { return (NP / 256) * bdw_chunks(rows); }
-
-extern "C" int trunet_bf16_dwconv_fwd(const void* zin, const float* s_in, const float* t_in, const float* w, const float* b,
-                                      void* zout, float* partials, int C, int K, int S, int Lin, int Lout, int NP, int N,
-                                      void* stream) {
-    if (!zin || !s_in || !t_in || !w || !b || !zout || !partials) return TRUNET_EINVAL;
-    if (C <= 0 || (C % 8) || NP <= 0 || (NP % 256) || N <= 0 || N > NP || Lin <= 0 || Lout != (Lin + 2 * (K / 2) - K) / S + 1)
-        return TRUNET_EINVAL;
-    const dim3 grid(NP / 256, C / 8, bdw_chunks(Lout));
-#define BDW_FWD(KK, SS) hipLaunchKernelGGL((bdw_fwd_kernel<KK, SS>), grid, dim3(256), 0, ST, (const u32x4*)zin, s_in, t_in, w, b, \
-                                           (u32x4*)zout, partials, C, Lin, Lout, NP, N)
-    if (K == 3 && S == 1) BDW_FWD(3, 1);
-    else if (K == 5 && S == 2) BDW_FWD(5, 2);
-    else if (K == 3 && S == 2) BDW_FWD(3, 2);
-    else return TRUNET_ENOTSUP;
-#undef BDW_FWD
-    return trunet_launch_status();
-}
-
-extern "C" int trunet_bf16_dwconv_bwd(const void* dy, const void* z, const float* ca, const float* cb, const float* cc,
-                                      const void* zin, const float* s_in, const float* t_in, const float* mean_in,
-                                      const float* w, void* dy_in, float* partials_in, float* w_partials, float* b_partials,
-                                      int C, int K, int S, int Lin, int Lout, int NP, int N, void* stream) {
-    if (!dy || !z || !ca || !cb || !cc || !zin || !s_in || !t_in || !mean_in || !w || !dy_in || !partials_in || !w_partials ||
-        !b_partials)
-        return TRUNET_EINVAL;
-    if (C <= 0 || (C % 8) || NP <= 0 || (NP % 256) || N <= 0 || N > NP || Lin <= 0 || Lout != (Lin + 2 * (K / 2) - K) / S + 1)
-        return TRUNET_EINVAL;
-    const dim3 grid(NP / 256, C / 8, bdw_chunks(Lin));
-#define BDW_BWD(KK, SS) hipLaunchKernelGGL((bdw_bwd_kernel<KK, SS>), grid, dim3(256), 0, ST, (const u32x4*)dy, (const u32x4*)z, ca, \
-                                           cb, cc, (const u32x4*)zin, s_in, t_in, mean_in, w, (u32x4*)dy_in, partials_in,           \
-                                           w_partials, b_partials, C, Lin, Lout, NP, N)
-    if (K == 3 && S == 1) BDW_BWD(3, 1);
-    else if (K == 5 && S == 2) BDW_BWD(5, 2);
-    else if (K == 3 && S == 2) BDW_BWD(3, 2);
-    else return TRUNET_ENOTSUP;
-#undef BDW_BWD
     return trunet_launch_status();
 }
 

@@ -1,7 +1,6 @@
 // Memory-bound stages of the TRU-Net body in the frames-last layout: layout changes, the first
-// (C_in -> 64) strided conv, depthwise convs (forward / backward), BatchNorm statistics -> affine,
-// AdamW.  All are HBM-bound: coalesced 16-byte accesses along the frame axis, one pass per tensor.
-#include <stdlib.h>
+// (C_in -> 64) strided conv, BatchNorm statistics -> affine, AdamW (the depthwise convs: depthwise.hip).
+// All are HBM-bound: coalesced 16-byte accesses along the frame axis, one pass per tensor.
 #include "common.hpp"
 
 namespace {
@@ -102,427 +101,8 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const float* __restrict
     }
 }
 
-// ---------------------------------------------------------------- depthwise conv forward
-constexpr int DW_PARTS = 16;
-
-template <int K>
-__global__ __launch_bounds__(256) void dwconv_fwd_kernel(const float* __restrict__ zin, const float* __restrict__ s_in,
-                                                         const float* __restrict__ t_in, const float* __restrict__ w,
-                                                         const float* __restrict__ b, float* __restrict__ zout,
-                                                         float* __restrict__ partials, int C, int S, int Lin, int Lout,
-                                                         int NP, int N) {
-    __shared__ double red[256];
-    const int c = blockIdx.y;
-    const int f4 = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    const float sc = s_in[c], sh = t_in[c], bb = b[c];
-    float wk[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) wk[k] = w[c * K + k];
-    const int ntn = NP / 128;
-    const int items = Lout * ntn;
-    float s1 = 0.f, s2 = 0.f;
-    for (int it = blockIdx.x * 8 + ly; it < items; it += gridDim.x * 8) {
-        const int nt = it / Lout, lo = it - nt * Lout;
-        const int n = nt * 128 + 4 * f4;
-        f32x4 acc = {bb, bb, bb, bb};
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int li = lo * S + k - K / 2;
-            if (li >= 0 && li < Lin) {
-                f32x4 v = *(const f32x4*)(zin + ((size_t)c * Lin + li) * NP + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = fmaf(wk[k], fmaxf(fmaf(v[e], sc, sh), 0.f), acc[e]);
-            }
-        }
-        *(f32x4*)(zout + ((size_t)c * Lout + lo) * NP + n) = acc;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (n + e < N) { s1 += acc[e]; s2 = fmaf(acc[e], acc[e], s2); }
-    }
-    double r1 = block_sum_f64((double)s1, red);
-    double r2 = block_sum_f64((double)s2, red);
-    if (threadIdx.x == 0) {
-        partials[((size_t)blockIdx.x * C + c) * 2 + 0] = (float)r1;
-        partials[((size_t)blockIdx.x * C + c) * 2 + 1] = (float)r2;
-    }
-}
-
-// ---------------------------------------------------------------- depthwise conv backward
-template <int K>
-__global__ __launch_bounds__(256) void dwconv_bwd_kernel(
-    const float* __restrict__ dy, const float* __restrict__ z, const float* __restrict__ ca,
-    const float* __restrict__ cb, const float* __restrict__ cc, const float* __restrict__ zin,
-    const float* __restrict__ s_in, const float* __restrict__ t_in, const float* __restrict__ mean_in,
-    const float* __restrict__ w, float* __restrict__ dy_in, float* __restrict__ partials_in,
-    float* __restrict__ w_partials, float* __restrict__ b_partials, int C, int S, int Lin, int Lout, int NP, int N) {
-    __shared__ double red[256];
-    const int c = blockIdx.y;
-    const int f4 = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    const float a0 = ca[c], a1 = cb[c], a2 = cc[c];
-    const float sc = s_in[c], sh = t_in[c], mu = mean_in[c];
-    float wk[K], dwk[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) { wk[k] = w[c * K + k]; dwk[k] = 0.f; }
-    float db = 0.f, s1 = 0.f, s2 = 0.f;
-    const int ntn = NP / 128;
-    const int items = Lin * ntn;
-    for (int it = blockIdx.x * 8 + ly; it < items; it += gridDim.x * 8) {
-        const int nt = it / Lin, li = it - nt * Lin;
-        const int n = nt * 128 + 4 * f4;
-        const f32x4 zi = *(const f32x4*)(zin + ((size_t)c * Lin + li) * NP + n);
-        f32x4 act, g = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) act[e] = fmaxf(fmaf(zi[e], sc, sh), 0.f);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int num = li + K / 2 - k;
-            const int lo = num / S;
-            if (num >= 0 && lo * S == num && lo < Lout) {
-                const size_t off = ((size_t)c * Lout + lo) * NP + n;
-                const f32x4 dv = *(const f32x4*)(dy + off);
-                const f32x4 zv = *(const f32x4*)(z + off);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float dz = (n + e < N) ? fmaf(a0, dv[e], fmaf(a1, zv[e], a2)) : 0.f;
-                    g[e] = fmaf(wk[k], dz, g[e]);
-                    dwk[k] = fmaf(dz, act[e], dwk[k]);
-                    if (k == K / 2) db += dz;
-                }
-            }
-        }
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            o[e] = (act[e] > 0.f) ? g[e] : 0.f;
-            s1 += o[e];
-            s2 = fmaf(o[e], zi[e] - mu, s2);
-        }
-        *(f32x4*)(dy_in + ((size_t)c * Lin + li) * NP + n) = o;
-    }
-    double r;
-    r = block_sum_f64((double)s1, red);
-    if (threadIdx.x == 0) partials_in[((size_t)blockIdx.x * C + c) * 2 + 0] = (float)r;
-    r = block_sum_f64((double)s2, red);
-    if (threadIdx.x == 0) partials_in[((size_t)blockIdx.x * C + c) * 2 + 1] = (float)r;
-    r = block_sum_f64((double)db, red);
-    if (threadIdx.x == 0) b_partials[(size_t)blockIdx.x * C + c] = (float)r;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        r = block_sum_f64((double)dwk[k], red);
-        if (threadIdx.x == 0) w_partials[((size_t)blockIdx.x * C + c) * K + k] = (float)r;
-    }
-}
-
-// ---------------------------------------------------------------- depthwise conv, sliding-window form
-// A thread owns (channel = blockIdx.y, 4 frames, chunk of positions = blockIdx.z) and walks the positions with the K
-// activated inputs (forward) / the three BatchNorm-backward-transformed dz rows a group of S input positions touches
-// (backward) in registers: every tensor row is loaded exactly once (the tap-gather form above re-reads taps through the
-// caches: 19 % more HBM traffic measured).  Statistics rows: partials[DW2_PARTS][C][2], part = chunk * DW2_FB + blockIdx.x.
-constexpr int DW2_FB = 32;                  // blocks over the frame quads (grid-stride)
-constexpr int DW2_CH = 4;                   // position chunks
-constexpr int DW2_PARTS = DW2_FB * DW2_CH;
-
-// every row is touched exactly once: non-temporal accesses keep them from evicting the neighbours' lines (same-box A/B:
-// -0.4 ms per step; -DTRUNET_DW_TEMPORAL builds the default-policy form)
-#ifndef TRUNET_DW_TEMPORAL
-#define DW2_LD(p) __builtin_nontemporal_load((const f32x4*)(p))
-#define DW2_ST(p, v) __builtin_nontemporal_store((v), (f32x4*)(p))
-#else
-#define DW2_LD(p) (*(const f32x4*)(p))
-#define DW2_ST(p, v) (*(f32x4*)(p) = (v))
-#endif
-template <int K, int S>
-__global__ __launch_bounds__(256) void dw2_fwd_kernel(const float* __restrict__ zin, const float* __restrict__ s_in,
-                                                      const float* __restrict__ t_in, const float* __restrict__ w,
-                                                      const float* __restrict__ b, float* __restrict__ zout,
-                                                      float* __restrict__ partials, int C, int Lin, int Lout, int NP, int N) {
-    __shared__ double red[256];
-    const int c = blockIdx.y;
-    const float sc = s_in[c], sh = t_in[c], bb = b[c];
-    float wk[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) wk[k] = w[c * K + k];
-    const int lo0 = (int)(((long long)blockIdx.z * Lout) / DW2_CH), lo1 = (int)(((long long)(blockIdx.z + 1) * Lout) / DW2_CH);
-    double s1 = 0.0, s2 = 0.0;       // per-thread sums in fp64: they feed cancelling BatchNorm expressions
-    for (int qd = blockIdx.x * 256 + threadIdx.x; qd < NP / 4; qd += DW2_FB * 256) {
-        const int n = 4 * qd;
-        const float* src = zin + (size_t)c * Lin * NP + n;
-        float* dst = zout + (size_t)c * Lout * NP + n;
-        auto load_act = [&](int li) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            if (li >= 0 && li < Lin) {
-                const f32x4 v = DW2_LD(src + (size_t)li * NP);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = fmaxf(fmaf(v[e], sc, sh), 0.f);
-            }
-            return a;
-        };
-        f32x4 win[K];                   // win[k] = activated input at li = lo*S + k - K/2
-#pragma unroll
-        for (int k = 0; k < K - S; ++k) win[k + S] = load_act(lo0 * S + k - K / 2);      // pre-shifted: the loop shifts first
-        for (int lo = lo0; lo < lo1; ++lo) {
-#pragma unroll
-            for (int k = 0; k < K - S; ++k) win[k] = win[k + S];
-#pragma unroll
-            for (int k = K - S; k < K; ++k) win[k] = load_act(lo * S + k - K / 2);
-            f32x4 acc = {bb, bb, bb, bb};
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = fmaf(wk[k], win[k][e], acc[e]);
-            DW2_ST(dst + (size_t)lo * NP, acc);
-            float r1 = 0.f, r2 = 0.f;        // the row's four frames in fp32, the running sums in fp64
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (n + e < N) { r1 += acc[e]; r2 = fmaf(acc[e], acc[e], r2); }
-            s1 += (double)r1;
-            s2 += (double)r2;
-        }
-    }
-    const int part = blockIdx.z * DW2_FB + blockIdx.x;
-    const double r1 = block_sum_f64(s1, red);
-    const double r2 = block_sum_f64(s2, red);
-    if (threadIdx.x == 0) {
-        partials[((size_t)part * C + c) * 2 + 0] = (float)r1;
-        partials[((size_t)part * C + c) * 2 + 1] = (float)r2;
-    }
-}
-
-template <int K, int S>
-__global__ __launch_bounds__(256) void dw2_bwd_kernel(
-    const float* __restrict__ dy, const float* __restrict__ z, const float* __restrict__ ca,
-    const float* __restrict__ cb, const float* __restrict__ cc, const float* __restrict__ zin,
-    const float* __restrict__ s_in, const float* __restrict__ t_in, const float* __restrict__ mean_in,
-    const float* __restrict__ w, float* __restrict__ dy_in, float* __restrict__ partials_in,
-    float* __restrict__ w_partials, float* __restrict__ b_partials, int C, int Lin, int Lout, int NP, int N) {
-    // groups of S input positions li = m*S + e; their taps touch the dz rows m - 1 .. m + 1 (K, S) in {(3,1), (5,2), (3,2)}
-    constexpr int LOMIN = -1, LOMAX = 1, W = 3;
-    static_assert((K == 3 && S == 1) || (K == 5 && S == 2) || (K == 3 && S == 2), "window derived for these shapes");
-    __shared__ double red[256];
-    const int c = blockIdx.y;
-    const float a0 = ca[c], a1 = cb[c], a2 = cc[c];
-    const float sc = s_in[c], sh = t_in[c], mu = mean_in[c];
-    float wk[K];
-    double dwk[K];                   // per-thread sums in fp64 (db and s1 cancel analytically in front of a BatchNorm)
-#pragma unroll
-    for (int k = 0; k < K; ++k) { wk[k] = w[c * K + k]; dwk[k] = 0.0; }
-    double db = 0.0, s1 = 0.0, s2 = 0.0;
-    const int G = (Lin + S - 1) / S;
-    const int m0 = (int)(((long long)blockIdx.z * G) / DW2_CH), m1 = (int)(((long long)(blockIdx.z + 1) * G) / DW2_CH);
-    for (int qd = blockIdx.x * 256 + threadIdx.x; qd < NP / 4; qd += DW2_FB * 256) {
-        const int n = 4 * qd;
-        const float* pdy = dy + (size_t)c * Lout * NP + n;
-        const float* pz = z + (size_t)c * Lout * NP + n;
-        const float* pin = zin + (size_t)c * Lin * NP + n;
-        float* pout = dy_in + (size_t)c * Lin * NP + n;
-        auto load_dz = [&](int lo) {
-            f32x4 d = {0.f, 0.f, 0.f, 0.f};
-            if (lo >= 0 && lo < Lout) {
-                const f32x4 dv = DW2_LD(pdy + (size_t)lo * NP);
-                const f32x4 zv = DW2_LD(pz + (size_t)lo * NP);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = (n + e < N) ? fmaf(a0, dv[e], fmaf(a1, zv[e], a2)) : 0.f;
-            }
-            return d;
-        };
-        f32x4 dzw[W];                   // dzw[i] = dz row m + LOMIN + i
-#pragma unroll
-        for (int i = 1; i < W; ++i) dzw[i] = load_dz(m0 + LOMIN + i - 1);                // pre-shifted
-        for (int m = m0; m < m1; ++m) {
-#pragma unroll
-            for (int i = 0; i < W - 1; ++i) dzw[i] = dzw[i + 1];
-            dzw[W - 1] = load_dz(m + LOMAX);
-#pragma unroll
-            for (int e = 0; e < S; ++e) {
-                const int li = m * S + e;
-                if (li >= Lin) continue;
-                const f32x4 zi = DW2_LD(pin + (size_t)li * NP);
-                f32x4 act, g = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) act[j] = fmaxf(fmaf(zi[j], sc, sh), 0.f);
-                // the four frames of a row are summed in fp32, the running sums are fp64
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    constexpr int half = K / 2;
-                    const int num = e + half - k;                        // relative to m*S; compile-time after unrolling
-                    if (((num % S) + S) % S != 0) continue;
-                    const int lo_rel = (num >= 0) ? num / S : -((-num) / S);
-                    const int wi = lo_rel - LOMIN;
-                    float rw = 0.f, rb = 0.f;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float dzv = dzw[wi][j];
-                        g[j] = fmaf(wk[k], dzv, g[j]);
-                        rw = fmaf(dzv, act[j], rw);
-                        rb += dzv;
-                    }
-                    dwk[k] += (double)rw;
-                    if (k == half) db += (double)rb;                      // e == 0 here: every dz row counted once
-                }
-                f32x4 o;
-                float r1 = 0.f, r2 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[j] = (act[j] > 0.f) ? g[j] : 0.f;
-                    r1 += o[j];
-                    r2 = fmaf(o[j], zi[j] - mu, r2);
-                }
-                s1 += (double)r1;
-                s2 += (double)r2;
-                DW2_ST(pout + (size_t)li * NP, o);
-            }
-        }
-    }
-    const int part = blockIdx.z * DW2_FB + blockIdx.x;
-    double r;
-    r = block_sum_f64(s1, red);
-    if (threadIdx.x == 0) partials_in[((size_t)part * C + c) * 2 + 0] = (float)r;
-    r = block_sum_f64(s2, red);
-    if (threadIdx.x == 0) partials_in[((size_t)part * C + c) * 2 + 1] = (float)r;
-    r = block_sum_f64(db, red);
-    if (threadIdx.x == 0) b_partials[(size_t)part * C + c] = (float)r;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        r = block_sum_f64(dwk[k], red);
-        if (threadIdx.x == 0) w_partials[((size_t)part * C + c) * K + k] = (float)r;
-    }
-}
-
-// The same backward WITHOUT reading z (the depthwise conv's own raw output, needed by its BatchNorm backward
-// dz = ca dy + cb z + cc): z[lo] = b + sum_k w[k] a[lo S + k - K/2] is recomputed from the activated input rows, which the
-// kernel holds anyway (mask, weight gradient) -- in dw2_fwd_kernel's order of operations, so it is the stored value bit
-// for bit.  One of the four row passes of the stride-1 layers (dy, z, zin in; dy_in out) goes away for K FMAs per
-// element.  The window of activated (and raw: statistics) input rows leads the group by K/2 + 1 rows:
-//   aw[i] = a[m S + i], i < AW = S + K/2 + 1;   z[m + 1] = b + sum_k w[k] aw[S - K/2 + k]
-// A chunk warms up over two extra groups (dz rows m0 - 1 and m0).  Loads are unconditional on clamped rows (a load inside
-// a branch makes hipcc drain the memory queue in front of it).
-template <int K, int S>
-__global__ __launch_bounds__(256) void dw2_bwd_rz_kernel(
-    const float* __restrict__ dy, const float* __restrict__ bias, const float* __restrict__ ca,
-    const float* __restrict__ cb, const float* __restrict__ cc, const float* __restrict__ zin,
-    const float* __restrict__ s_in, const float* __restrict__ t_in, const float* __restrict__ mean_in,
-    const float* __restrict__ w, float* __restrict__ dy_in, float* __restrict__ partials_in,
-    float* __restrict__ w_partials, float* __restrict__ b_partials, int C, int Lin, int Lout, int NP, int N) {
-    constexpr int LOMIN = -1, W = 3;
-    constexpr int AW = S + K / 2 + 1, ZO = S - K / 2;
-    static_assert((K == 3 && S == 1) || (K == 5 && S == 2) || (K == 3 && S == 2), "window derived for these shapes");
-    __shared__ double red[256];
-    const int c = blockIdx.y;
-    const float a0 = ca[c], a1 = cb[c], a2 = cc[c];
-    const float sc = s_in[c], sh = t_in[c], mu = mean_in[c], bb = bias[c];
-    // the statistics' zin - mean from the activation where it is > 0 (elsewhere the masked gradient is 0): a = sc zin + sh.
-    // sc == 0 (BatchNorm weight exactly zero; uniform over the block): a does not carry zin, the row is read again.
-    // (precision of a / sc - (sh / sc + mean): eps (|zin| + |sh / sc|); an offset beyond 2^16 times the scale: re-read as well)
-    const bool sc0 = fabsf(sc) < 1e-30f || fabsf(sh) > 65536.f * fabsf(sc);
-    const float isc = sc0 ? 0.f : 1.f / sc, zoff = fmaf(sh, isc, mu);
-    float wk[K];
-    double dwk[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) { wk[k] = w[c * K + k]; dwk[k] = 0.0; }
-    double db = 0.0, s1 = 0.0, s2 = 0.0;
-    const int G = (Lin + S - 1) / S;
-    const int m0 = (int)(((long long)blockIdx.z * G) / DW2_CH), m1 = (int)(((long long)(blockIdx.z + 1) * G) / DW2_CH);
-    for (int qd = blockIdx.x * 256 + threadIdx.x; qd < NP / 4; qd += DW2_FB * 256) {
-        const int n = 4 * qd;
-        const float* pdy = dy + (size_t)c * Lout * NP + n;
-        const float* pin = zin + (size_t)c * Lin * NP + n;
-        float* pout = dy_in + (size_t)c * Lin * NP + n;
-        f32x4 aw[AW];                   // activated input rows m*S + i
-        auto load_row = [&](int li, f32x4& act) {
-            const bool ok = li >= 0 && li < Lin;
-            const f32x4 raw = DW2_LD(pin + (size_t)min(max(li, 0), Lin - 1) * NP);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) act[j] = ok ? fmaxf(fmaf(raw[j], sc, sh), 0.f) : 0.f;
-        };
-        f32x4 dzw[W];                   // dzw[i] = dz row m + LOMIN + i
-#pragma unroll
-        for (int i = 0; i < W; ++i) dzw[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int ms = m0 - 2;          // two warm-up groups: dz rows m0 - 1, m0
-#pragma unroll
-        for (int i = S; i < AW; ++i) load_row(ms * S + i - S, aw[i]);      // pre-shifted: the loop shifts first
-        for (int m = ms; m < m1; ++m) {
-#pragma unroll
-            for (int i = 0; i < AW - S; ++i) aw[i] = aw[i + S];
-#pragma unroll
-            for (int i = AW - S; i < AW; ++i) load_row(m * S + i, aw[i]);
-#pragma unroll
-            for (int i = 0; i < W - 1; ++i) dzw[i] = dzw[i + 1];
-            {
-                const int lo = m + 1;
-                const bool ok = lo >= 0 && lo < Lout;
-                const f32x4 dv = DW2_LD(pdy + (size_t)min(max(lo, 0), Lout - 1) * NP);
-                f32x4 zrec = {bb, bb, bb, bb};
-#pragma unroll
-                for (int k = 0; k < K; ++k)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) zrec[j] = fmaf(wk[k], aw[ZO + k][j], zrec[j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    dzw[W - 1][j] = (ok && n + j < N) ? fmaf(a0, dv[j], fmaf(a1, zrec[j], a2)) : 0.f;
-            }
-            if (m < m0) continue;
-#pragma unroll
-            for (int e = 0; e < S; ++e) {
-                const int li = m * S + e;
-                if (li >= Lin) continue;
-                const f32x4 act = aw[e];
-                f32x4 zc;                                                 // zin - mean
-#pragma unroll
-                for (int j = 0; j < 4; ++j) zc[j] = fmaf(act[j], isc, -zoff);
-                if (sc0) {
-                    const f32x4 zi = DW2_LD(pin + (size_t)li * NP);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) zc[j] = zi[j] - mu;
-                }
-                f32x4 g = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    constexpr int half = K / 2;
-                    const int num = e + half - k;                        // relative to m*S; compile-time after unrolling
-                    if (((num % S) + S) % S != 0) continue;
-                    const int lo_rel = (num >= 0) ? num / S : -((-num) / S);
-                    const int wi = lo_rel - LOMIN;
-                    float rw = 0.f, rb = 0.f;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float dzv = dzw[wi][j];
-                        g[j] = fmaf(wk[k], dzv, g[j]);
-                        rw = fmaf(dzv, act[j], rw);
-                        rb += dzv;
-                    }
-                    dwk[k] += (double)rw;
-                    if (k == half) db += (double)rb;                      // e == 0 here: every dz row counted once
-                }
-                f32x4 o;
-                float r1 = 0.f, r2 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[j] = (act[j] > 0.f) ? g[j] : 0.f;
-                    r1 += o[j];
-                    r2 = fmaf(o[j], zc[j], r2);
-                }
-                s1 += (double)r1;
-                s2 += (double)r2;
-                DW2_ST(pout + (size_t)li * NP, o);
-            }
-        }
-    }
-    const int part = blockIdx.z * DW2_FB + blockIdx.x;
-    double r;
-    r = block_sum_f64(s1, red);
-    if (threadIdx.x == 0) partials_in[((size_t)part * C + c) * 2 + 0] = (float)r;
-    r = block_sum_f64(s2, red);
-    if (threadIdx.x == 0) partials_in[((size_t)part * C + c) * 2 + 1] = (float)r;
-    r = block_sum_f64(db, red);
-    if (threadIdx.x == 0) b_partials[(size_t)part * C + c] = (float)r;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        r = block_sum_f64(dwk[k], red);
-        if (threadIdx.x == 0) w_partials[((size_t)part * C + c) * K + k] = (float)r;
-    }
-}
-
 // ---------------------------------------------------------------- activation backward at a block boundary
+constexpr int DW_PARTS = 16;
 // A stand-alone block class (network.py:9-120) receives the cotangent of its POST-activation output, the fused
 // schedule works on gradients of the BatchNorm output: dy *= [sc[c] z + sh[c] > 0] in place (sc == NULL: [z > 0],
 // StandardConv1d's plain ReLU) and, with mean != NULL, the BatchNorm-backward sums of the result
@@ -968,88 +548,6 @@ extern "C" int trunet_conv_first_fwd(const float* x, const float* w, const float
     if (K == 5 && Cin == 3) hipLaunchKernelGGL((conv_first_kernel<3, 5>), grid, block, 0, ST, x, w, b, y, Cout, S, Lin, Lout, NP);
     else if (K == 5 && Cin == 4) hipLaunchKernelGGL((conv_first_kernel<4, 5>), grid, block, 0, ST, x, w, b, y, Cout, S, Lin, Lout, NP);
     else return TRUNET_ENOTSUP;
-    return trunet_launch_status();
-}
-
-// TRUNET_DW_GATHER=1: the tap-gather kernels for every shape (A/B measurements)
-static bool dw_gather_forced() {
-    static const bool v = [] { const char* e = getenv("TRUNET_DW_GATHER"); return e && e[0] == '1'; }();
-    return v;
-}
-
-extern "C" int trunet_dwconv_nparts(int Lout) { (void)Lout; return DW2_PARTS; }
-extern "C" int trunet_dwconv_bwd_nparts(int Lin) { (void)Lin; return DW2_PARTS; }
-
-extern "C" int trunet_dwconv_fwd(const float* zin, const float* s_in, const float* t_in, const float* w, const float* b,
-                                 float* zout, float* partials, int C, int K, int S, int Lin, int Lout, int NP, int N,
-                                 void* stream) {
-    if (!zin || !s_in || !t_in || !w || !b || !zout || !partials || (NP % 128)) return TRUNET_EINVAL;
-    if (!dw_gather_forced() && Lout == (Lin + 2 * (K / 2) - K) / S + 1 &&
-        ((K == 3 && S == 1) || (K == 5 && S == 2) || (K == 3 && S == 2))) {
-        const dim3 g2(DW2_FB, C, DW2_CH);
-#define DW2_FWD(KK, SS) hipLaunchKernelGGL((dw2_fwd_kernel<KK, SS>), g2, dim3(256), 0, ST, zin, s_in, t_in, w, b, zout, partials, C, \
-                                           Lin, Lout, NP, N)
-        if (K == 3 && S == 1) DW2_FWD(3, 1);
-        else if (K == 5) DW2_FWD(5, 2);
-        else DW2_FWD(3, 2);
-#undef DW2_FWD
-        return trunet_launch_status();
-    }
-    dim3 grid(DW2_PARTS, C);            // other shapes: the tap-gather form, one statistics row per block as well
-    if (K == 3) hipLaunchKernelGGL(dwconv_fwd_kernel<3>, grid, dim3(256), 0, ST, zin, s_in, t_in, w, b, zout, partials, C, S, Lin, Lout, NP, N);
-    else if (K == 5) hipLaunchKernelGGL(dwconv_fwd_kernel<5>, grid, dim3(256), 0, ST, zin, s_in, t_in, w, b, zout, partials, C, S, Lin, Lout, NP, N);
-    else return TRUNET_ENOTSUP;
-    return trunet_launch_status();
-}
-
-extern "C" int trunet_dwconv_bwd(const float* dy, const float* z, const float* ca, const float* cb, const float* cc,
-                                 const float* zin, const float* s_in, const float* t_in, const float* mean_in,
-                                 const float* w, float* dy_in, float* partials_in, float* w_partials, float* b_partials,
-                                 int C, int K, int S, int Lin, int Lout, int NP, int N, void* stream) {
-    if (!dy || !z || !ca || !cb || !cc || !zin || !s_in || !t_in || !mean_in || !w || !dy_in || !partials_in ||
-        !w_partials || !b_partials || (NP % 128))
-        return TRUNET_EINVAL;
-    if (!dw_gather_forced() && Lout == (Lin + 2 * (K / 2) - K) / S + 1 &&
-        ((K == 3 && S == 1) || (K == 5 && S == 2) || (K == 3 && S == 2))) {
-        const dim3 g2(DW2_FB, C, DW2_CH);
-#define DW2_BWD(KK, SS) hipLaunchKernelGGL((dw2_bwd_kernel<KK, SS>), g2, dim3(256), 0, ST, dy, z, ca, cb, cc, zin, s_in, t_in,   \
-                                           mean_in, w, dy_in, partials_in, w_partials, b_partials, C, Lin, Lout, NP, N)
-        if (K == 3 && S == 1) DW2_BWD(3, 1);
-        else if (K == 5) DW2_BWD(5, 2);
-        else DW2_BWD(3, 2);
-#undef DW2_BWD
-        return trunet_launch_status();
-    }
-    dim3 grid(DW2_PARTS, C);
-    if (K == 3) hipLaunchKernelGGL(dwconv_bwd_kernel<3>, grid, dim3(256), 0, ST, dy, z, ca, cb, cc, zin, s_in, t_in, mean_in, w, dy_in, partials_in, w_partials, b_partials, C, S, Lin, Lout, NP, N);
-    else if (K == 5) hipLaunchKernelGGL(dwconv_bwd_kernel<5>, grid, dim3(256), 0, ST, dy, z, ca, cb, cc, zin, s_in, t_in, mean_in, w, dy_in, partials_in, w_partials, b_partials, C, S, Lin, Lout, NP, N);
-    else return TRUNET_ENOTSUP;
-    return trunet_launch_status();
-}
-
-// trunet_dwconv_bwd without the z operand: z is recomputed from (zin, w, bias) as trunet_dwconv_fwd computed it
-// (TRUNET_ENOTSUP for shapes the sliding-window kernels do not cover: call trunet_dwconv_bwd with z then)
-extern "C" int trunet_dwconv_bwd_rz(const float* dy, const float* bias, const float* ca, const float* cb, const float* cc,
-                                    const float* zin, const float* s_in, const float* t_in, const float* mean_in,
-                                    const float* w, float* dy_in, float* partials_in, float* w_partials, float* b_partials,
-                                    int C, int K, int S, int Lin, int Lout, int NP, int N, void* stream) {
-    if (!dy || !bias || !ca || !cb || !cc || !zin || !s_in || !t_in || !mean_in || !w || !dy_in || !partials_in ||
-        !w_partials || !b_partials || (NP % 128))
-        return TRUNET_EINVAL;
-    static const bool off = [] { const char* e = getenv("TRUNET_DW_RZ"); return e && e[0] == '0'; }();
-    if (off || dw_gather_forced() || Lout != (Lin + 2 * (K / 2) - K) / S + 1 ||
-        !((K == 3 && S == 1) || (K == 5 && S == 2) || (K == 3 && S == 2)))
-        return TRUNET_ENOTSUP;
-    // few output positions: the two warm-up groups per chunk and the four-row window cost more than the z row they save
-    // (encoder.5, k3 s2, 32 -> 16 positions: 331 us against 308 us for the z-reading kernel)
-    if (Lout < 32 && !(getenv("TRUNET_DW_RZ") && getenv("TRUNET_DW_RZ")[0] == '2')) return TRUNET_ENOTSUP;
-    const dim3 g2(DW2_FB, C, DW2_CH);
-#define DW2_BWD(KK, SS) hipLaunchKernelGGL((dw2_bwd_rz_kernel<KK, SS>), g2, dim3(256), 0, ST, dy, bias, ca, cb, cc, zin, s_in,  \
-                                           t_in, mean_in, w, dy_in, partials_in, w_partials, b_partials, C, Lin, Lout, NP, N)
-    if (K == 3 && S == 1) DW2_BWD(3, 1);
-    else if (K == 5) DW2_BWD(5, 2);
-    else DW2_BWD(3, 2);
-#undef DW2_BWD
     return trunet_launch_status();
 }
 
