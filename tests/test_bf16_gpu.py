@@ -259,8 +259,8 @@ def _run_wgrad(N, P, M, dz, z, co, segs, Wshape, ldw_m, ldw_c):
         a.a_mode, a.a1, a.ac0, a.ac1, a.ac2 = PRO_BNBWD, ptr16(z16), ptr(co[0]), ptr(co[1]), ptr(co[2])
     else:
         a.a_mode = PRO_NONE
-    wp = torch.zeros(npw * numel, device=DEV)
-    bp = torch.zeros(npw * M, device=DEV)
+    wp = torch.full((npw * numel,), float("nan"), device=DEV)      # every image and bias row must be written by its workgroup
+    bp = torch.full((npw * M,), float("nan"), device=DEV)
     a.w_partials, a.b_partials, a.b_stride, a.b_off = ptr(wp), ptr(bp), M, 0
     check(lib.trunet_bf16_wgrad(a, st), "bf16_wgrad")
     torch.cuda.synchronize()
