@@ -532,6 +532,32 @@ int trunet_resample_stream(const float* hist, const float* in, float* out, const
                            int taps_in_lds, void* stream);
 int trunet_resample_stream_commit(float* hist, const float* in, const int64_t* plan, int half, int K, int p, int q, int n_sess,
                                   int slots, int64_t n_in, void* stream);
+/* trunet_highband_gains / trunet_highband_join (highband.py): the band above 8 kHz of audio at fs > 16 kHz
+ * around the 16 kHz enhancement.  lo, y16 (total_samples each): the utterances at 16 kHz before and after the enhancement,
+ * packed back to back; sample_off, frame_off: int64 DEVICE prefixes of L_b and of T_b = 1 + L_b / 128; hp: the
+ * TRUNET_HB_TAPS taps of the zero-phase high-pass; energy: scratch of 2 total_frames floats.
+ * trunet_highband_gains: g (total_frames), g[t] = clamp(sqrt((e_y + 1e-10) / (e_x + 1e-10)), g_min, 1) with e_x, e_y the
+ *   energies of hp * lo and hp * y16 ("same", zeros outside the utterance) over [128 t - 256, 128 t + 256) n [0, L_b);
+ *   0 < g_min <= 1.  Two launches (hop-block energies, then the frames); every sum runs in a fixed order, no atomics.
+ * trunet_highband_join: out[n] = up_y[n] + G[n] (x[n] - up_x[n]) per utterance, n < L_b.  x, out (total_samples at fs) are
+ *   packed by sample_off; up_y, up_x (total_up each) by up_off, utterance b having at least L_b samples there; pd / qd =
+ *   16000 / fs in lowest terms, pd < qd <= 640.  TRUNET_HB_KEEP: G = 1, g and frame_off may be NULL.  TRUNET_HB_FOLLOW:
+ *   G[n] = (1 - a) g[t0] + a g[min(t0 + 1, T_b - 1)], t0 = n pd / (128 qd), a = (n pd % (128 qd)) / (128 qd), with g and
+ *   frame_off as trunet_highband_gains leaves them for L16_b = ceil(L_b pd / qd).
+ * Totals below 2^31.  TRUNET_EINVAL without a launch for anything the host can see; an utterance whose device offsets
+ * contradict each other is skipped.  Results are bit for bit independent of the batch. */
+#define TRUNET_HB_TAPS 63
+#define TRUNET_HB_RUN 16                    /* hop blocks of one utterance a workgroup of the energy kernel owns */
+#define TRUNET_HB_JOIN_TILE 4096            /* samples of one utterance a workgroup of the join owns */
+#define TRUNET_HB_KEEP 1
+#define TRUNET_HB_FOLLOW 2
+int trunet_highband_gains(const float* lo, const float* y16, const int64_t* sample_off, const int64_t* frame_off,
+                          const float* hp, float* energy, float* g, int B, int64_t total_samples, int64_t total_frames,
+                          float g_min, void* stream);
+int trunet_highband_join(const float* up_y, const float* up_x, const float* x, const float* g, float* out,
+                         const int64_t* sample_off, const int64_t* up_off, const int64_t* frame_off, int B,
+                         int64_t total_samples, int64_t total_up, int64_t total_frames, int pd, int qd, int mode,
+                         void* stream);
 size_t trunet_stoi_workspace_bytes(int B, int64_t total_frames, int64_t total_segments);
 int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, const int64_t* frame_off, const int64_t* seg_off,
                        const int64_t* chunk_off, const float* window, const int* band_edges, const float* tw512,

@@ -7,7 +7,8 @@ offline path of ``util.loss_fn`` -- centred rect STFT with reflect padding and P
 (``dataset.py:56-76,246-272``), the network in eval mode, phase-aware mask and ``torch.istft(..., length=L)``
 (``phm.py:31-45``, ``dataset.py:293-296``) -- and does not depend on which other utterances share the call, their order,
 or the chunking of the frames.  Audio at another rate (``fs=``, 8 to 96 kHz) is resampled to 16 kHz and back on the GPU
-around the same call (resample.py).  A call is
+around the same call (resample.py); ``highband="keep"`` or ``"follow"`` carries the band above 8 kHz,
+which the resampler's low-pass removes, around the network (highband.py).  A call is
 
     pack          the utterances back to back + their offset tables (one host -> device copy)
     features      trunet_stft_features_ragged (+ trunet_pcen_ragged for C_in = 4): one launch each for the whole batch
@@ -25,6 +26,7 @@ other layer acts per frame with eval BatchNorm.
 Command line (the ``denoise.py`` role)::
 
     python -m tinyrecurrentunet_amd.enhance --checkpoint CKPT --input-size {3,4} [--use-tgru] --in DIR --out DIR [--resample]
+    ... --resample [--highband {drop,keep,follow}] [--highband-floor-db DB]
 """
 import argparse
 import math
@@ -100,7 +102,8 @@ def _inputs(x, lengths):
 
 
 @torch.no_grad()
-def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAMPLE_RATE):
+def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAMPLE_RATE, highband="drop",
+            highband_floor_db=-30.0):
     """Denoise recordings of any lengths with ``net`` (a ``network.TRUNet`` in eval mode, on the GPU).
 
     x: a list of 1-D fp32 cuda tensors -> list of 1-D tensors of the same lengths; or a (B, Lmax) tensor with ``lengths``
@@ -111,10 +114,17 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     always runs the layer kernels, the only ones that carry the block over whole sequences); "int8" quantizes the net's
     current weights once per call (quantize.QuantizedTRUNet, stateless nets only).
     fs: the sample rate of ``x``.  At another rate than 16 kHz the audio is resampled to 16 kHz on the GPU
-    (resample.resample), enhanced, resampled back and cut to exactly each input's length; the band above 8 kHz is not
-    restored.  Every utterance then needs at least 257 samples at 16 kHz."""
+    (resample.resample), enhanced, resampled back and cut to exactly each input's length.  Every utterance then needs at
+    least 257 samples at 16 kHz.
+    highband: what becomes of the band above 8 kHz when ``fs`` is above 16 kHz.  "drop" (default): the band above 8 kHz is
+    not restored.  "keep": the input's band is added back as it was.  "follow": it is added back attenuated, frame by
+    frame, by the suppression the network applied between 4 and 8 kHz, never below ``highband_floor_db`` (at most 0 dB)
+    and never amplified (highband.rejoin).  At ``fs`` <= 16 kHz there is no such band: the result is
+    that of "drop"."""
     if path not in PATHS:
         raise ValueError("path must be one of %s, got %r" % (PATHS, path))
+    from .highband import check_args
+    highband, highband_floor_db = check_args(highband, highband_floor_db)
     if max_frames is None:
         max_frames = MAX_FRAMES
     if int(max_frames) != max_frames or max_frames < 1:
@@ -125,7 +135,7 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     if net.use_tgru and path in ("folded", "int8"):
         raise ValueError("use_tgru runs the layer kernels (frames_per_seq): path=%r carries no sequence" % path)
     if fs != SAMPLE_RATE:
-        return _enhance_at(net, x, lengths, beta, max_frames, path, fs)
+        return _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband, highband_floor_db)
     xs, width = _inputs(x, lengths)
     for b, t in enumerate(xs):
         if t.shape[0] < MIN_SAMPLES:
@@ -179,9 +189,10 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     return Y
 
 
-def _enhance_at(net, x, lengths, beta, max_frames, path, fs):
+def _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband="drop", floor_db=-30.0):
     """enhance() for audio at ``fs``: resample -> enhance at 16 kHz -> resample back -> cut to the input lengths.
-    ceil(ceil(L p / q) q / p) >= L, so there is always enough to cut."""
+    ceil(ceil(L p / q) q / p) >= L, so there is always enough to cut.  With ``highband`` "keep" or "follow" and ``fs``
+    above 16 kHz the way back is highband.rejoin, which adds the input's band above 8 kHz to the resampled result."""
     from . import resample as R
     p, q = R.ratio(fs, SAMPLE_RATE)
     xs, width = _inputs(x, lengths)
@@ -193,7 +204,11 @@ def _enhance_at(net, x, lengths, beta, max_frames, path, fs):
     lens = [int(t.shape[0]) for t in xs]
     down = R.resample(xs, fs, SAMPLE_RATE)
     den = enhance(net, down, beta=beta, max_frames=max_frames, path=path)
-    up = R.resample(den, SAMPLE_RATE, fs)
+    if highband != "drop" and p < q and xs:
+        from .highband import rejoin
+        up = rejoin(xs, down, den, fs, highband, floor_db)
+    else:
+        up = R.resample(den, SAMPLE_RATE, fs)
     if width is None:
         return [y[:n] for y, n in zip(up, lens)]
     Y = torch.zeros((len(xs), width), device=up[0].device if up else x.device, dtype=torch.float32)
@@ -300,7 +315,7 @@ def main(argv=None):
                                  description="Denoise every 16 kHz *.wav of a folder with a trained TRU-Net (HIP, MI355X).  "
                                              "With --resample, files at other rates are resampled to 16 kHz on the GPU, "
                                              "denoised and written back at their own rate; the band above 8 kHz is not "
-                                             "restored.")
+                                             "restored unless --highband says so.")
     ap.add_argument("--checkpoint", required=True, help="train.py checkpoint ({'model_state_dict': ...}) or a state_dict")
     ap.add_argument("--input-size", type=int, choices=(3, 4), required=True, help="feature channels the net was trained on")
     ap.add_argument("--use-tgru", action="store_true", help="the net was trained with the time-recurrent block")
@@ -310,8 +325,21 @@ def main(argv=None):
     ap.add_argument("--path", choices=PATHS, default="auto", help="network path (default auto)")
     ap.add_argument("--resample", action="store_true",
                     help="accept files at other rates than 16 kHz (8 to 96 kHz): resample to 16 kHz, denoise, resample "
-                         "back; every file keeps its rate and sample count, the band above 8 kHz is not restored")
+                         "back; every file keeps its rate and sample count")
+    ap.add_argument("--highband", choices=("drop", "keep", "follow"), default="drop",
+                    help="with --resample, for files above 16 kHz: drop (default): the band above 8 kHz is not restored; "
+                         "keep: the input's band is added back as it was; follow: added back with the suppression the "
+                         "network applied between 4 and 8 kHz.  Files at 16 kHz and below are unaffected")
+    ap.add_argument("--highband-floor-db", type=float, default=-30.0,
+                    help="--highband follow: the most the band above 8 kHz is attenuated, in dB (default -30)")
     args = ap.parse_args(argv)
+    if not args.resample and (args.highband != "drop" or args.highband_floor_db != -30.0):
+        ap.error("--highband and --highband-floor-db go with --resample")
+    from .highband import check_args
+    try:
+        check_args(args.highband, args.highband_floor_db)
+    except ValueError as e:
+        ap.error(str(e))
 
     from scipy.io.wavfile import write as wavwrite
     from .dataset import _read_wav
@@ -341,7 +369,8 @@ def main(argv=None):
         max_samples = max(1, int(math.floor(args.max_seconds * rate)))
         for chunk in _batches([xs[i].shape[0] for i in group], max_samples):
             idx = [group[k] for k in chunk]
-            ys = enhance(net, [xs[i].cuda() for i in idx], path=args.path, fs=rate)
+            ys = enhance(net, [xs[i].cuda() for i in idx], path=args.path, fs=rate, highband=args.highband,
+                         highband_floor_db=args.highband_floor_db)
             for i, y in zip(idx, ys):
                 q16 = torch.clamp(torch.round(y * 32768.0), -32768, 32767).to(torch.int16).cpu().numpy()
                 wavwrite(os.path.join(args.outdir, names[i]), rate, q16)
