@@ -565,6 +565,26 @@ int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, const int64_t* 
                        int64_t total_frames, int64_t total_segments, int64_t total_chunks, void* stream);
 int trunet_si_sdr_ragged(const float* clean, const float* estimate, const int64_t* sample_off, const int64_t* chunk_off,
                          double* partials, double* out, int B, int64_t total_samples, int64_t total_chunks, void* stream);
+/* The intelligibility loss -(lambda / B) sum_b s_b, s_b the STOI (extended = 0) or ESTOI (1) above (stoi_loss.py, DESIGN
+ * section 3q).  Its forward is trunet_stoi_ragged; the backward reads that call's inputs and its workspace (kept frames,
+ * counts, band magnitudes), all of the clean signal being a constant.
+ * trunet_stoi_loss_bwd: grad (total_samples) = d loss / d estimate at 10 kHz, with scale = -lambda / B and gout the (1,)
+ *   DEVICE cotangent of the loss; an utterance without a segment gets exact zeros.  bwd_workspace:
+ *   trunet_stoi_loss_workspace_bytes(B, total_frames, total_segments) bytes.  Four launches (segments, frame gather, bands,
+ *   samples), no atomics: an utterance's gradient is bit for bit independent of its batch-mates.
+ * trunet_resample_ragged_bwd: the adjoint of trunet_resample_ragged for one plane: gin (total_in) from gout (total_out).
+ * trunet_stoi_loss_value: out[0] = (float)(-mean_b scores[b]) (fp64, b ascending), out[1] = lambda * out[0];
+ *   loss_accum (may be NULL): loss_accum[0] += out[1]. */
+size_t trunet_stoi_loss_workspace_bytes(int B, int64_t total_frames, int64_t total_segments);
+int trunet_stoi_loss_bwd(const float* sig, const int64_t* sig_off, const int64_t* frame_off, const int64_t* seg_off,
+                         const int64_t* chunk_off, const float* window, const int* band_edges, const float* tw512,
+                         const void* fwd_workspace, void* bwd_workspace, const float* gout, double scale, int extended,
+                         float* grad, int B, int64_t total_samples, int64_t total_frames, int64_t total_segments,
+                         int64_t total_chunks, void* stream);
+int trunet_resample_ragged_bwd(const float* gout, float* gin, const int64_t* in_off, const int64_t* out_off,
+                               const float* taps, int half, int p, int q, int B, int64_t total_in, int64_t total_out,
+                               void* stream);
+int trunet_stoi_loss_value(const double* scores, int B, float lambda, float* out, float* loss_accum, void* stream);
 
 /* ---- the train step's loss as util.loss_fn composes it (util.py:239-250, stft_loss.py:141-166), fused (round 4) ----
  * trunet_stft_loss_fwdgrad: trunet_stft_loss_fwd's three sums per frame AND the two coefficient-free gradient frames of the

@@ -226,6 +226,10 @@ def _declare(L):
         "trunet_stoi_workspace_bytes": [i, i64, i64],
         "trunet_stoi_ragged": [p] * 12 + [i, i64, i64, i64, i64, p],
         "trunet_si_sdr_ragged": [p, p, p, p, p, p, i, i64, i64, p],
+        "trunet_stoi_loss_workspace_bytes": [i, i64, i64],
+        "trunet_stoi_loss_bwd": [p] * 11 + [d, i, p, i, i64, i64, i64, i64, p],
+        "trunet_resample_ragged_bwd": [p, p, p, p, p, i, i, i, i, i64, i64, p],
+        "trunet_stoi_loss_value": [p, i, f, p, p, p],
         "trunet_loss_scratch_bytes": [],
         "trunet_loss_finalize": [C.POINTER(LossArgs), p, p, p, p],
         "trunet_loss_grad_gather": [C.POINTER(LossGatherArgs), p, p, p, p, p, i, i, p],
@@ -278,6 +282,7 @@ def _declare(L):
     L.trunet_stream_fwd_scratch_floats.restype = C.c_size_t
     L.trunet_loss_scratch_bytes.restype = C.c_size_t
     L.trunet_stoi_workspace_bytes.restype = C.c_size_t
+    L.trunet_stoi_loss_workspace_bytes.restype = C.c_size_t
     L.trunet_reverb_workspace_bytes.restype = C.c_size_t
     L.trunet_rir_ism_workspace_bytes.restype = C.c_size_t
     L.trunet_wave_loss_workspace_bytes.restype = C.c_size_t

@@ -2,6 +2,7 @@
 //   * polyphase resampler (fs -> 10 kHz, Kaiser-windowed sinc, the closed form of scipy.signal.resample_poly)
 //   * STOI / ESTOI: silent-frame removal, fused overlap-add + 512-point STFT + third-octave bands, 30-frame segments
 //   * SI-SDR on the signals at their own rate
+//   * the backward of STOI / ESTOI as a loss in the estimate (stoi_loss.py), which reads the forward's workspace
 // Every buffer is sized by what the host knows from the lengths (frames BEFORE silence removal), so a call needs no
 // device -> host copy: the kept-frame count K_b lives on the device only and the later kernels read it.  No float atomics:
 // every per-utterance reduction runs in a fixed order inside that utterance's own workgroups, so an utterance's results are
@@ -380,6 +381,316 @@ __global__ __launch_bounds__(256) void si_sdr_finalize_kernel(const double* __re
     out[b] = 10.0 * log10(tgt / res);
 }
 
+// ---------------------------------------------------------------- STOI / ESTOI loss: the backward (stoi_loss.py, section 3q)
+// The loss is -(1 / B) sum_b s_b with s_b the STOI or ESTOI above; everything computed from the clean signal (the kept-frame
+// list, its bands, the clip level) is a constant.  The forward is trunet_stoi_ragged itself, whose workspace the backward
+// reads: kept, count, tob.  Four launches, each sized by the ragged tables; every sum has a fixed order, no atomics.
+constexpr int SEGCELLS = NSEG * NBAND;   // cotangents one segment hands to its 30 frames
+
+struct StoiBwdArgs {
+    double* dseg;                        // (nG, 30, 15) per segment: d(segment score) / d tob_y[s + t][k]
+    double* dtob;                        // (nF, 15)     d loss / d tob_y
+    int* inv;                            // (nF)         analysis frame -> its slot in kept, -1 when dropped
+    float* dframe;                       // (nF, 256)    w[s] * cotangent of STFT frame j of the silence-free estimate
+    const float* gout;                   // (1) cotangent of the loss
+    double scale;                        // -lambda / B
+    int extended;
+    float* grad;                         // (nS) d loss / d estimate at 10 kHz
+};
+
+// stoi_segments_kernel's grid and staging; one wave per segment writes the 30 x 15 cotangents of its estimate bands.
+// STOI (lane k < 15 owns band k): u_t = y_t nx / ny, y'_t = min(u_t, c x_t) with the gradient on the branch the forward took
+// (u_t <= c x_t: the first), d = sxy / ((sqrt sxx + eps)(sqrt syy + eps)).  ESTOI (lane t < 30 owns frame t): the column
+// correlation back through the column and the row normalisation.  sqrt has derivative 0 at 0 throughout.
+__global__ __launch_bounds__(256) void stoi_segments_bwd_kernel(StoiArgs a, StoiBwdArgs g) {
+    __shared__ float tb[2][SEG_WG + NSEG - 1][NBAND];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t c = blockIdx.x;
+    const int b = prefix_find(a.co, a.B, c);
+    StoiUtt u;
+    if (!stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) || c < u.c0) return;
+    const int nseg = min(a.count[b], u.F) - NSEG;
+    const int s0 = (int)(c - u.c0) * SEG_WG;
+    if (s0 >= nseg) return;
+    const int s1 = min(s0 + SEG_WG, nseg);
+    const int rows = s1 - s0 + NSEG - 1;
+    for (int i = tid; i < 2 * rows * NBAND; i += 256) {
+        const int sig = i / (rows * NBAND), r = (i / NBAND) % rows, k = i % NBAND;
+        tb[sig][r][k] = a.tob[((size_t)sig * a.nF + u.f0 + s0 + r) * NBAND + k];
+    }
+    __syncthreads();
+    const double clipc = 1.0 + 5.623413251903491;
+    for (int s = s0 + w; s < s1; s += 4) {
+        const int r0 = s - s0;
+        double* out = g.dseg + (size_t)(u.g0 + s) * SEGCELLS;
+        if (!g.extended) {
+            if (lane >= NBAND) continue;
+            const int k = lane;
+            double nx = 0.0, sy = 0.0;
+            for (int t = 0; t < NSEG; ++t) {
+                const double xv = tb[0][r0 + t][k], yv = tb[1][r0 + t][k];
+                nx += xv * xv;
+                sy += yv * yv;
+            }
+            nx = sqrt(nx);
+            const double rsy = sqrt(sy), ny = rsy + DEPS;
+            double mxs = 0.0, mys = 0.0;
+            for (int t = 0; t < NSEG; ++t) {
+                const double xv = tb[0][r0 + t][k];
+                mxs += xv;
+                mys += fmin((double)tb[1][r0 + t][k] * nx / ny, xv * clipc);
+            }
+            const double mx = mxs / NSEG, my = mys / NSEG;
+            double sxx = 0.0, syy = 0.0, sxy = 0.0;
+            for (int t = 0; t < NSEG; ++t) {
+                const double xv = tb[0][r0 + t][k];
+                const double dx = xv - mx, dy = fmin((double)tb[1][r0 + t][k] * nx / ny, xv * clipc) - my;
+                sxx += dx * dx;
+                syy += dy * dy;
+                sxy += dx * dy;
+            }
+            const double A = sqrt(sxx) + DEPS, rs = sqrt(syy), Bn = rs + DEPS;
+            const double P = 1.0 / (A * Bn), Q = syy > 0.0 ? sxy / (A * Bn * Bn * rs) : 0.0;
+            // h_t = d d / d y'_t on the unclipped cells (the mean removal is self-adjoint on sum-zero rows), hy = sum h_t y_t
+            double hy = 0.0, hm = 0.0;
+            for (int t = 0; t < NSEG; ++t) {
+                const double xv = tb[0][r0 + t][k], yv = tb[1][r0 + t][k];
+                const double uv = yv * nx / ny, cv = xv * clipc;
+                hm += P * (xv - mx) - Q * (fmin(uv, cv) - my);
+            }
+            hm /= NSEG;
+            for (int t = 0; t < NSEG; ++t) {
+                const double xv = tb[0][r0 + t][k], yv = tb[1][r0 + t][k];
+                const double uv = yv * nx / ny, cv = xv * clipc;
+                const double h = uv <= cv ? P * (xv - mx) - Q * (fmin(uv, cv) - my) - hm : 0.0;
+                hy += h * yv;
+            }
+            const double al = nx / ny, be = sy > 0.0 ? hy * nx / (ny * ny * rsy) : 0.0;
+            for (int t = 0; t < NSEG; ++t) {
+                const double xv = tb[0][r0 + t][k], yv = tb[1][r0 + t][k];
+                const double uv = yv * nx / ny, cv = xv * clipc;
+                const double h = uv <= cv ? P * (xv - mx) - Q * (fmin(uv, cv) - my) - hm : 0.0;
+                out[t * NBAND + k] = al * h - be * yv;
+            }
+            continue;
+        }
+        // ESTOI rows, as the forward: band k's mean, sqrt of the centred sum of squares, and that + eps
+        const int k = min(lane, NBAND - 1);
+        double rm[2], rq[2];
+#pragma unroll
+        for (int sig = 0; sig < 2; ++sig) {
+            double m = 0.0;
+            for (int t = 0; t < NSEG; ++t) m += tb[sig][r0 + t][k];
+            m /= NSEG;
+            double q = 0.0;
+            for (int t = 0; t < NSEG; ++t) {
+                const double v = tb[sig][r0 + t][k] - m;
+                q += v * v;
+            }
+            rm[sig] = m;
+            rq[sig] = sqrt(q);
+        }
+        const int t = min(lane, NSEG - 1);
+        double xc[NBAND], yc[NBAND];
+        double cmx = 0.0, cmy = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < NBAND; ++kk) {
+            const double m0 = __shfl(rm[0], kk), n0 = __shfl(rq[0], kk) + DEPS;
+            const double m1 = __shfl(rm[1], kk), n1 = __shfl(rq[1], kk) + DEPS;
+            xc[kk] = (tb[0][r0 + t][kk] - m0) / n0;
+            yc[kk] = (tb[1][r0 + t][kk] - m1) / n1;
+            cmx += xc[kk];
+            cmy += yc[kk];
+        }
+        cmx /= NBAND;
+        cmy /= NBAND;
+        double qx = 0.0, qy = 0.0, dot = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < NBAND; ++kk) {
+            xc[kk] -= cmx;
+            yc[kk] -= cmy;
+            qx += xc[kk] * xc[kk];
+            qy += yc[kk] * yc[kk];
+        }
+#pragma unroll
+        for (int kk = 0; kk < NBAND; ++kk) dot += xc[kk] * yc[kk];
+        const double Ax = sqrt(qx) + DEPS, ry = sqrt(qy), Ay = ry + DEPS;
+        const double live = lane < NSEG ? 1.0 / NSEG : 0.0;             // the segment score is the mean of the 30 columns
+        const double U = live / (Ax * Ay), V = qy > 0.0 ? live * dot / (Ax * Ay * Ay * ry) : 0.0;
+        // G[kk]: cotangent of the row-normalised estimate at (kk, t), after the adjoint of the column-mean removal
+        double gm = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < NBAND; ++kk) {
+            xc[kk] = U * xc[kk] - V * yc[kk];
+            gm += xc[kk];
+        }
+        gm /= NBAND;
+#pragma unroll
+        for (int kk = 0; kk < NBAND; ++kk) {
+            const double G = xc[kk] - gm;
+            const double m1 = __shfl(rm[1], kk), r1 = __shfl(rq[1], kk), n1 = r1 + DEPS;
+            const double cv = (double)tb[1][r0 + t][kk] - m1;          // the centred band value
+            const double gsum = wave_sum_f64(G);                        // lanes >= 30 hold 0
+            const double gc = wave_sum_f64(G * cv);
+            const double v = (G - gsum / NSEG) / n1 - (r1 > 0.0 ? gc / (n1 * n1 * r1) * cv : 0.0);
+            if (lane < NSEG) out[t * NBAND + kk] = v;
+        }
+    }
+}
+
+// one thread per (analysis frame slot j, band k): d loss / d tob_y[j][k] = factor * the cotangents of the up to 30 segments
+// that hold STFT frame j, added with s ascending; factor = scale * gout / (segments * (15 | 1)).  The band-0 thread also
+// writes the inverse of the kept-frame list for source frame j (a binary search: kept is ascending).
+__global__ __launch_bounds__(256) void stoi_dtob_kernel(StoiArgs a, StoiBwdArgs g) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.nF * NBAND) return;
+    const int64_t fr = i / NBAND;
+    const int k = (int)(i - fr * NBAND);
+    const int b = prefix_find(a.fo, a.B, fr);
+    StoiUtt u;
+    if (!stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) || fr < u.f0 || fr >= u.f0 + u.F) return;
+    const int K = min(a.count[b], u.F), nseg = K - NSEG;
+    const int j = (int)(fr - u.f0);
+    if (k == 0) {
+        const int* kept = a.kept + u.f0;
+        int lo = 0, hi = K;                                           // first slot with kept[slot] >= j
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (kept[mid] < j) lo = mid + 1; else hi = mid;
+        }
+        g.inv[fr] = lo < K && kept[lo] == j ? lo : -1;
+    }
+    double acc = 0.0;
+    if (nseg > 0 && j <= K - 2) {
+        for (int s = max(j - (NSEG - 1), 0); s <= min(j, nseg - 1); ++s)
+            acc += g.dseg[(size_t)(u.g0 + s) * SEGCELLS + (j - s) * NBAND + k];
+        acc *= g.scale * (double)g.gout[0] / ((double)nseg * (g.extended ? 1 : NBAND));
+    }
+    g.dtob[fr * NBAND + k] = acc;
+}
+
+// stoi_bands_kernel's grid and frame pairing, for the estimate alone: the transform again, dZ_k = (dtob / tob) Z_k on the
+// bins of a band (0 where tob is 0) and 0 elsewhere, and the adjoint of the zero-padded real transform: frames j and j + 1
+// come back as the real and imaginary parts of one inverse FFT of the Hermitian extension (dZ_k + conj dZ_{512-k}) / 2.
+__global__ __launch_bounds__(256) void stoi_bands_bwd_kernel(StoiArgs a, StoiBwdArgs g, const cpx* __restrict__ tw) {
+    __shared__ cpx sa[SNFFT], sb[SNFFT];
+    __shared__ float rat[2][NBAND + 1];
+    __shared__ int ed[NBAND + 1];
+    const int tid = threadIdx.x;
+    const int64_t fr = blockIdx.x;
+    const int b = prefix_find(a.fo, a.B, fr);
+    StoiUtt u;
+    if (!stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) || fr < u.f0 || fr >= u.f0 + u.F) return;
+    const int K = min(a.count[b], u.F);
+    const int j = (int)(fr - u.f0);
+    if (K <= NSEG || (j & 1) || j >= K - 1) return;               // uniform over the workgroup
+    const bool two = j + 1 < K - 1;
+    const int* kept = a.kept + u.f0;
+    const float* x = a.sig + (size_t)a.nS + u.s0;
+    sa[tid] = make_float2(sil_frame(x, a.win, kept, u.F, j, tid), two ? sil_frame(x, a.win, kept, u.F, j + 1, tid) : 0.f);
+    sa[tid + SF] = make_float2(0.f, 0.f);
+    if (tid < 2 * NBAND) {
+        const int f = tid / NBAND, k = tid - f * NBAND;
+        float r = 0.f;
+        if (f == 0 || two) {
+            const double t = (double)a.tob[((size_t)a.nF + fr + f) * NBAND + k];
+            r = t > 0.0 ? (float)(g.dtob[(fr + f) * NBAND + k] / t) : 0.f;
+        }
+        rat[f][k] = r;
+    }
+    if (tid <= NBAND) ed[tid] = min(max(a.edges[tid], 1), SNFFT / 2);   // bins 1 .. 255: none is its own mirror
+    cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    cpx* Cb = Z == sa ? sb : sa;
+    for (int i = tid; i < SNFFT; i += 256) {
+        const int k = i <= SNFFT / 2 ? i : SNFFT - i;
+        int band = -1;
+        for (int q = 0; q < NBAND; ++q)
+            if (k >= ed[q] && k < max(ed[q + 1], ed[q])) band = q;
+        cpx v = make_float2(0.f, 0.f);
+        if (band >= 0) {
+            cpx A, B2;
+            split_pair(Z, k, SNFFT, A, B2);
+            const float ra = 0.5f * rat[0][band], rb = 0.5f * rat[1][band];
+            A = make_float2(ra * A.x, ra * A.y);
+            B2 = make_float2(rb * B2.x, rb * B2.y);
+            v = i == k ? make_float2(A.x - B2.y, A.y + B2.x) : make_float2(A.x + B2.y, B2.x - A.y);
+        }
+        Cb[i] = v;
+    }
+    const cpx* d = fft_lds_t<9, true>(Cb, Z, tw);
+    const float ws = a.win[tid];
+    g.dframe[(size_t)fr * SF + tid] = ws * d[tid].x;
+    if (two) g.dframe[(size_t)(fr + 1) * SF + tid] = ws * d[tid].y;
+}
+
+// one thread per 10 kHz sample m of the estimate: the adjoint of sil_frame's windowing and of the overlap-add of the kept
+// frames, as a gather.  m lies in the analysis frames m / 128 - 1 and m / 128; a kept one sits at slot k = inv[.] and puts m
+// at n = 128 k + s of the silence-free signal, which STFT frames n / 128 - 1 and n / 128 read.
+__global__ __launch_bounds__(256) void stoi_signal_bwd_kernel(StoiArgs a, StoiBwdArgs g) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.nS) return;
+    const int b = prefix_find(a.so, a.B, i);
+    StoiUtt u;
+    float acc = 0.f;
+    if (stoi_utt(a.so, a.fo, a.go, a.co, b, a.nS, a.nF, a.nG, a.nC, u) && i >= u.s0 && i - u.s0 < (int64_t)u.F * SHOP + SF) {
+        const int K = min(a.count[b], u.F);
+        const int m = (int)(i - u.s0);
+        if (K > NSEG) {
+            for (int fi = m / SHOP - 1; fi <= m / SHOP; ++fi) {
+                if (fi < 0 || fi >= u.F) continue;
+                const int s = m - fi * SHOP;
+                const int k = g.inv[u.f0 + fi];
+                if (k < 0 || k >= K) continue;
+                const int n = k * SHOP + s;
+                float dys = 0.f;
+                for (int j = n / SHOP - 1; j <= n / SHOP; ++j)
+                    if (j >= 0 && j <= K - 2) dys += g.dframe[(size_t)(u.f0 + j) * SF + n - j * SHOP];
+                acc += a.win[s] * dys;
+            }
+        }
+    }
+    g.grad[i] = acc;
+}
+
+// adjoint of resample_poly_kernel as a gather per input sample: dx[n] = p sum_m h[m q - n p + L] dy[m] over the outputs m
+// of the same utterance whose tap index lies in [0, 2L], m ascending.  grid (ceil(total_in / 256)).
+__global__ __launch_bounds__(256) void resample_poly_bwd_kernel(const float* __restrict__ gy, float* __restrict__ gx,
+                                                                const int64_t* __restrict__ io,
+                                                                const int64_t* __restrict__ oo,
+                                                                const float* __restrict__ taps, int half, int p, int q,
+                                                                int B, int64_t nIn, int64_t nOut) {
+    extern __shared__ float h[];
+    const int ntaps = 2 * half + 1;
+    for (int i = threadIdx.x; i < ntaps; i += 256) h[i] = taps[i];
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nIn) return;
+    const int b = prefix_find(io, B, g);
+    const int64_t i0 = io[b], i1 = io[b + 1], o0 = oo[b], o1 = oo[b + 1];
+    float acc = 0.f;
+    if (i0 >= 0 && i1 <= nIn && i1 >= i0 && o0 >= 0 && o1 <= nOut && o1 - o0 == ((i1 - i0) * p + q - 1) / q && g >= i0 &&
+        g < i1) {
+        const int64_t np = (g - i0) * p, M = o1 - o0;
+        const int64_t lo = np > half ? (np - half + q - 1) / q : 0;
+        const int64_t hi = min((np + half) / q, M - 1);
+        const float* y = gy + o0;
+        for (int64_t m = lo; m <= hi; ++m) acc += h[m * q - np + half] * y[m];
+    }
+    gx[g] = (float)p * acc;
+}
+
+// out[0] = (float)(-mean_b score_b) in fp64, b ascending; out[1] = lambda * out[0]; loss_accum (may be null) += out[1]
+__global__ void stoi_loss_value_kernel(const double* __restrict__ score, int B, float lambda, float* __restrict__ out,
+                                       float* __restrict__ loss_accum) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += score[b];
+    const float v = (float)(-(s / B));
+    out[0] = v;
+    out[1] = lambda * v;
+    if (loss_accum) loss_accum[0] += lambda * v;
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -441,6 +752,76 @@ extern "C" int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, cons
         hipLaunchKernelGGL(stoi_segments_kernel, dim3((unsigned)total_chunks), dim3(256), 0, ST, a);
     }
     hipLaunchKernelGGL(stoi_finalize_kernel, dim3(B), dim3(256), 0, ST, a);
+    return trunet_launch_status();
+}
+
+extern "C" size_t trunet_stoi_loss_workspace_bytes(int B, int64_t total_frames, int64_t total_segments) {
+    if (B <= 0 || total_frames < 0 || total_segments < 0) return 0;
+    return align256(total_segments * SEGCELLS * sizeof(double)) + align256(total_frames * NBAND * sizeof(double)) +
+           align256(total_frames * sizeof(int)) + align256(total_frames * SF * sizeof(float));
+}
+
+extern "C" int trunet_stoi_loss_bwd(const float* sig, const int64_t* sig_off, const int64_t* frame_off,
+                                    const int64_t* seg_off, const int64_t* chunk_off, const float* window,
+                                    const int* band_edges, const float* tw512, const void* fwd_workspace,
+                                    void* bwd_workspace, const float* gout, double scale, int extended, float* grad, int B,
+                                    int64_t total_samples, int64_t total_frames, int64_t total_segments,
+                                    int64_t total_chunks, void* stream) {
+    if (!sig || !sig_off || !frame_off || !seg_off || !chunk_off || !window || !band_edges || !tw512 || !fwd_workspace ||
+        !bwd_workspace || !gout || !grad || B <= 0 || total_samples < 0 || total_samples > ((int64_t)1 << 40) ||
+        !(scale == scale) || (extended != 0 && extended != 1))
+        return TRUNET_EINVAL;
+    if (total_frames < 0 || total_frames > total_samples / SHOP || total_frames > 0x7fffffffLL ||
+        total_segments < 0 || total_segments > total_frames || total_chunks * SEG_WG < total_segments ||
+        total_chunks * SEG_WG > total_segments + (int64_t)B * (SEG_WG - 1))
+        return TRUNET_EINVAL;
+    if (total_samples == 0) return TRUNET_OK;
+    char* w = (char*)fwd_workspace;                             // trunet_stoi_ragged's layout
+    StoiArgs a;
+    a.sig = sig; a.so = sig_off; a.fo = frame_off; a.go = seg_off; a.co = chunk_off; a.win = window; a.edges = band_edges;
+    a.energy = (double*)w;   w += align256(total_frames * sizeof(double));
+    a.kept = (int*)w;        w += align256(total_frames * sizeof(int));
+    a.count = (int*)w;       w += align256(B * sizeof(int));
+    a.tob = (float*)w;       w += align256(2 * total_frames * NBAND * sizeof(float));
+    a.seg = (double*)w;
+    a.stoi = nullptr; a.estoi = nullptr; a.segments = nullptr;
+    a.B = B; a.nS = total_samples; a.nF = total_frames; a.nG = total_segments; a.nC = total_chunks;
+    char* v = (char*)bwd_workspace;
+    StoiBwdArgs g;
+    g.dseg = (double*)v;     v += align256(total_segments * SEGCELLS * sizeof(double));
+    g.dtob = (double*)v;     v += align256(total_frames * NBAND * sizeof(double));
+    g.inv = (int*)v;         v += align256(total_frames * sizeof(int));
+    g.dframe = (float*)v;
+    g.gout = gout; g.scale = scale; g.extended = extended; g.grad = grad;
+    if (total_chunks > 0) {
+        hipLaunchKernelGGL(stoi_segments_bwd_kernel, dim3((unsigned)total_chunks), dim3(256), 0, ST, a, g);
+    }
+    if (total_frames > 0) {
+        hipLaunchKernelGGL(stoi_dtob_kernel, dim3((unsigned)((total_frames * NBAND + 255) / 256)), dim3(256), 0, ST, a, g);
+        hipLaunchKernelGGL(stoi_bands_bwd_kernel, dim3((unsigned)total_frames), dim3(256), 0, ST, a, g, (const cpx*)tw512);
+    }
+    hipLaunchKernelGGL(stoi_signal_bwd_kernel, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, ST, a, g);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_resample_ragged_bwd(const float* gout, float* gin, const int64_t* in_off, const int64_t* out_off,
+                                          const float* taps, int half, int p, int q, int B, int64_t total_in,
+                                          int64_t total_out, void* stream) {
+    if (!gout || !gin || !in_off || !out_off || !taps || half < 0 || half > MAX_HALF_TAPS || p < 1 || p > 64 || q < 1 ||
+        q > 64 || B <= 0 || total_in < 0 || total_out < 0 || total_in > ((int64_t)1 << 40))
+        return TRUNET_EINVAL;
+    if (total_out * q < total_in * p || total_out * q >= total_in * p + (int64_t)B * q) return TRUNET_EINVAL;
+    if (total_in == 0) return TRUNET_OK;
+    hipLaunchKernelGGL(resample_poly_bwd_kernel, dim3((unsigned)((total_in + 255) / 256)), dim3(256),
+                       (2 * half + 1) * sizeof(float), ST, gout, gin, in_off, out_off, taps, half, p, q, B, total_in,
+                       total_out);
+    return trunet_launch_status();
+}
+
+extern "C" int trunet_stoi_loss_value(const double* scores, int B, float lambda, float* out, float* loss_accum,
+                                      void* stream) {
+    if (!scores || !out || B <= 0 || !(lambda == lambda)) return TRUNET_EINVAL;
+    hipLaunchKernelGGL(stoi_loss_value_kernel, dim3(1), dim3(64), 0, ST, scores, B, lambda, out, loss_accum);
     return trunet_launch_status();
 }
 

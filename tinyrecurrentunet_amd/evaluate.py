@@ -114,6 +114,56 @@ def _check_args(clean, estimate, lengths, fs, metrics):
     return xs, ys, pq, metrics
 
 
+def _stoi_forward(sig, op, tot, p, q, B):
+    """Steps 3 and 4 of ``evaluate`` on the packed (2, nS) signals -> (stoi, estoi, segments, sig10, workspace).  The
+    workspace holds what trunet_stoi_ragged left (kept frames, counts, band magnitudes): stoi_loss.py's backward reads it,
+    and shares this forward so that the loss scores are evaluate's bit for bit."""
+    lib, st, dev = L.lib(), L.stream(), sig.device
+    nS = tot[0]
+    # 3. resample to 10 kHz (each plane of sig / sig10 is nS / nR wide whenever it holds a sample)
+    nR = tot[2]
+    if (p, q) == (1, 1) or nS == 0:
+        sig10 = sig
+    else:
+        taps = _taps(p, q, dev)
+        sig10 = torch.empty((2, nR), device=dev, dtype=torch.float32)
+        check(lib.trunet_resample_ragged(ptr(sig), ptr(sig10), op[0], op[2], ptr(taps), (taps.shape[0] - 1) // 2, p, q, B,
+                                         nS, nR, 2, st), "resample_ragged")
+
+    # 4. STOI / ESTOI
+    win, edges = _window_edges(dev)
+    nF, nG, nC = tot[3], tot[4], tot[5]
+    ws = torch.empty(int(lib.trunet_stoi_workspace_bytes(B, nF, nG)), device=dev, dtype=torch.uint8)
+    stoi = torch.empty(B, device=dev, dtype=torch.float64)
+    estoi = torch.empty(B, device=dev, dtype=torch.float64)
+    segments = torch.empty(B, device=dev, dtype=torch.int64)
+    check(lib.trunet_stoi_ragged(sig10.data_ptr(), op[2], op[3], op[4], op[5], ptr(win), edges.data_ptr(),
+                                 ptr(L.twiddles(NFFT, dev)), ws.data_ptr(), stoi.data_ptr(), estoi.data_ptr(),
+                                 segments.data_ptr(), B, nR, nF, nG, nC, st), "stoi_ragged")
+    return stoi, estoi, segments, sig10, ws
+
+
+def _window_edges(dev):
+    return (_const("window", dev, lambda: torch.tensor(window(), dtype=torch.float32, device=dev)),
+            _const("edges", dev, lambda: torch.tensor(band_edges(), dtype=torch.int32, device=dev)))
+
+
+def _taps(p, q, dev):
+    return _const(("taps", p, q), dev, lambda: torch.tensor(kaiser_filter(p, q)[0], dtype=torch.float32, device=dev))
+
+
+def _tables(lens, p, q):
+    """the six int64 prefix tables of a batch (samples, SI-SDR chunks, resampled samples, frames, segments, segment
+    workgroups) -> (offs (6, B + 1) numpy, their totals)"""
+    res = [-(-n * p // q) for n in lens]
+    frames = [n_frames(r) for r in res]
+    segs = [max(f - SEG, 0) for f in frames]
+    rows = [lens, [-(-n // SDR_CHUNK) for n in lens], res, frames, segs, [-(-s // SEG_WG) for s in segs]]
+    offs = np.zeros((6, len(lens) + 1), dtype=np.int64)
+    offs[:, 1:] = np.cumsum(np.array(rows, dtype=np.int64), axis=1)
+    return offs, [int(v) for v in offs[:, -1]]
+
+
 @torch.no_grad()
 def evaluate(clean, estimate, lengths=None, fs=16000, metrics=METRICS):
     """STOI / ESTOI / SI-SDR of every (clean, estimate) pair -> dict of (B,) cuda tensors (float64; ``segments`` int64)."""
@@ -129,14 +179,7 @@ def evaluate(clean, estimate, lengths=None, fs=16000, metrics=METRICS):
     lib, st = L.lib(), L.stream()
 
     # 1. pack: sample, SI-SDR chunk, resampled sample, frame, segment and segment-workgroup prefix tables
-    lens = [int(x.shape[0]) for x in xs]
-    res = [-(-n * p // q) for n in lens]
-    frames = [n_frames(r) for r in res]
-    segs = [max(f - SEG, 0) for f in frames]
-    rows = [lens, [-(-n // SDR_CHUNK) for n in lens], res, frames, segs, [-(-s // SEG_WG) for s in segs]]
-    offs = np.zeros((6, B + 1), dtype=np.int64)
-    offs[:, 1:] = np.cumsum(np.array(rows, dtype=np.int64), axis=1)
-    tot = [int(v) for v in offs[:, -1]]
+    offs, tot = _tables([int(x.shape[0]) for x in xs], p, q)
     offs_d = torch.from_numpy(offs).to(dev)
     op = [offs_d[i].data_ptr() for i in range(6)]
     nS = tot[0]
@@ -155,27 +198,8 @@ def evaluate(clean, estimate, lengths=None, fs=16000, metrics=METRICS):
     if not want_stoi:
         return out
 
-    # 3. resample to 10 kHz (each plane of sig / sig10 is nS / nR wide whenever it holds a sample)
-    nR = tot[2]
-    if (p, q) == (1, 1) or nS == 0:
-        sig10 = sig
-    else:
-        taps = _const(("taps", p, q), dev, lambda: torch.tensor(kaiser_filter(p, q)[0], dtype=torch.float32, device=dev))
-        sig10 = torch.empty((2, nR), device=dev, dtype=torch.float32)
-        check(lib.trunet_resample_ragged(ptr(sig), ptr(sig10), op[0], op[2], ptr(taps), (taps.shape[0] - 1) // 2, p, q, B,
-                                         nS, nR, 2, st), "resample_ragged")
-
-    # 4. STOI / ESTOI
-    win = _const("window", dev, lambda: torch.tensor(window(), dtype=torch.float32, device=dev))
-    edges = _const("edges", dev, lambda: torch.tensor(band_edges(), dtype=torch.int32, device=dev))
-    nF, nG, nC = tot[3], tot[4], tot[5]
-    ws = torch.empty(int(lib.trunet_stoi_workspace_bytes(B, nF, nG)), device=dev, dtype=torch.uint8)
-    stoi = torch.empty(B, device=dev, dtype=torch.float64)
-    estoi = torch.empty(B, device=dev, dtype=torch.float64)
-    segments = torch.empty(B, device=dev, dtype=torch.int64)
-    check(lib.trunet_stoi_ragged(sig10.data_ptr(), op[2], op[3], op[4], op[5], ptr(win), edges.data_ptr(),
-                                 ptr(L.twiddles(NFFT, dev)), ws.data_ptr(), stoi.data_ptr(), estoi.data_ptr(),
-                                 segments.data_ptr(), B, nR, nF, nG, nC, st), "stoi_ragged")
+    # 3., 4. resample to 10 kHz, then STOI / ESTOI
+    stoi, estoi, segments = _stoi_forward(sig, op, tot, p, q, B)[:3]
     if "stoi" in metrics:
         out["stoi"] = stoi
     if "estoi" in metrics:

@@ -91,13 +91,17 @@ def _fl_boundary(net, plan):
 class _FusedLossFn(torch.autograd.Function):
     """net output (B*T, 8, 257), clean (B, L) -> (loss, vals); vals = [loss, l1, stft_sc, stft_mag, ...] (no gradient).
     With ``wave`` (the time-domain terms of cos_loss.py) -> (loss, vals, wave vals): the terms are added
-    to ``loss`` on the device by two more launches forward and one more backward; vals[0] stays the loss without them."""
+    to ``loss`` on the device by two more launches forward and one more backward; vals[0] stays the loss without them.
+    With ``stoi`` (the intelligibility term of stoi_loss.py) the tuple ends with its (2,) values
+    [term, weighted term]: its forward adds the weighted term to ``loss`` on the device, its backward adds the cotangent
+    into the audio gradient before the mask + iSTFT backward."""
 
     @staticmethod
-    def forward(ctx, net_out, clean, T, beta, stft_lambda, res, sc_lambda, mag_lambda, wave=None, fl=None):
+    def forward(ctx, net_out, clean, T, beta, stft_lambda, res, sc_lambda, mag_lambda, wave=None, fl=None, stoi=None):
         # res: [(padded window, n, hop, win_length), ...] (empty: L1 only)
         # wave: None or (g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps), g = () without the cosine term
         # fl: None, or the _lib.FramesLast hand-off whose tensor net_out is: [8][257][NP], the network's own output buffer
+        # stoi: None or (stoi_lambda, extended)
         net_out = net_out.contiguous()
         B = (net_out.shape[0] if fl is None else fl.N) // T
         Ln = (T - 1) * HOP
@@ -141,18 +145,24 @@ class _FusedLossFn(torch.autograd.Function):
         loss = torch.empty((), device=dev, dtype=torch.float32)
         vals = torch.empty(5 + 2 * L.MAX_RES, device=dev, dtype=torch.float32)
         check(lib.trunet_loss_finalize(a, ptr(loss), ptr(vals), scratch.data_ptr(), st), "loss_finalize")
-        ctx.planes, ctx.T, ctx.beta, ctx.wave, ctx.fl = planes, T, beta, None, fl
+        ctx.planes, ctx.T, ctx.beta, ctx.wave, ctx.fl, ctx.stoi = planes, T, beta, None, fl, None
+        tail = ()
+        if stoi is not None:
+            from . import stoi_loss as stl
+            run = stl.forward_packed(audio.reshape(-1), clean[:, :Ln].reshape(-1), [Ln] * B, *stl.ev.ratio(16000), stoi[1])
+            tail = (stl.loss_value(run, stoi[0], loss_accum=loss),)
+            ctx.stoi = (run, stoi[0])
         if wave is None:
             ctx.save_for_backward(net_out, clean, audio, tw, vals)
-            ctx.mark_non_differentiable(vals)
-            return loss, vals
+            ctx.mark_non_differentiable(vals, *tail)
+            return (loss, vals) + tail
         from . import cos_loss as cl
         g, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps = wave
         ctx.wave = cl.wave_plan(Ln, g, si_sdr_lambda > 0, dev)
         wvals, _, coef = cl.wave_forward(audio, clean, ctx.wave, cos_lambda, cos_eps, si_sdr_lambda, si_sdr_eps, loss_accum=loss)
         ctx.save_for_backward(net_out, clean, audio, tw, vals, coef)
-        ctx.mark_non_differentiable(vals, wvals)
-        return loss, vals, wvals
+        ctx.mark_non_differentiable(vals, wvals, *tail)
+        return (loss, vals, wvals) + tail
 
     @staticmethod
     def backward(ctx, g_loss, *_g_vals):
@@ -169,6 +179,9 @@ class _FusedLossFn(torch.autograd.Function):
         if ctx.wave is not None:
             from . import cos_loss as cl
             cl.wave_backward(audio, clean, ctx.wave, ctx.saved_tensors[5], g_loss, g)
+        if ctx.stoi is not None:
+            from . import stoi_loss as stl
+            g += stl.backward_packed(ctx.stoi[0], g_loss, ctx.stoi[1]).view(B, Ln)
         g_net = torch.empty_like(net_out)
         if ctx.fl is None:
             check(lib.trunet_mask_istft_bwd(ptr(g), ptr(net_out), ptr(g_net), ptr(tw), B, ctx.T, Ln, ctx.beta, st), "mask_istft_bwd")
@@ -181,7 +194,7 @@ class _FusedLossFn(torch.autograd.Function):
                                                ctx.beta, st), "mask_istft_bwd_fl")
             ticket.cotangent = g_net
         ctx.planes = None
-        return g_net, None, None, None, None, None, None, None, None, None
+        return g_net, None, None, None, None, None, None, None, None, None, None
 
 
 def _fused_loss_plan(mrstftloss, stft_lambda, dev):
@@ -218,13 +231,21 @@ def _wave_terms(cos_lambda, cos_config, si_sdr_lambda, si_sdr_eps):
 
 
 def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, cos_lambda=0, cos_config=None, si_sdr_lambda=0,
-            si_sdr_eps=1e-8, **kwargs):
+            si_sdr_eps=1e-8, stoi_lambda=0, stoi_config=None, **kwargs):
     """util.py:186-251 (R7).  X = (clean_audio, noisy_audio), each (B, 1, L) (a leading batch-1 dim as the
     reference's DataLoader gives, util.py:207, is squeezed).  Returns (loss, {"l1", "stft_sc", "stft_mag"}).
 
     Opt-in time-domain terms (cos_loss.py): loss += cos_lambda * CosSimLoss(**cos_config)(audio, clean)
     + si_sdr_lambda * SISDRLoss(si_sdr_eps)(audio, clean); cos_config = {"eps": ..., "g": ...} like stft_config.  The
-    dictionary then also carries "cos" and / or "si_sdr", the weighted terms.  Without them nothing changes."""
+    dictionary then also carries "cos" and / or "si_sdr", the weighted terms.  Without them nothing changes.
+
+    Opt-in intelligibility term (stoi_loss.py): loss += stoi_lambda * STOILoss(**stoi_config)(audio, clean)
+    at 16 kHz, stoi_config = {"extended": bool}; the dictionary then carries "stoi", the weighted term."""
+    stoi = None
+    if bool(stoi_lambda) and stoi_lambda > 0:
+        stoi = (float(stoi_lambda), bool((stoi_config or {}).get("extended", False)))
+        if set(stoi_config or {}) - {"extended"}:
+            raise ValueError("stoi_config takes \"extended\" only, got %s" % sorted(stoi_config))
     clean_audio, noisy_audio = X
     if clean_audio.dim() == 4:
         clean_audio, noisy_audio = clean_audio.squeeze(0), noisy_audio.squeeze(0)
@@ -246,7 +267,11 @@ def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, cos
     if plan is not None:
         fused = (out, clean.float(), T, 0.5, float(stft_lambda) if plan else 0.0, plan,
                  float(mrstftloss.sc_lambda) if plan else 0.0, float(mrstftloss.mag_lambda) if plan else 0.0)
-        if wave is None and fl is None:
+        if stoi is not None:
+            res = _FusedLossFn.apply(*fused, wave, fl, stoi)
+            loss, vals, svals = res[0], res[1], res[-1]
+            wvals = res[2] if wave is not None else None
+        elif wave is None and fl is None:
             loss, vals = _FusedLossFn.apply(*fused)
         elif wave is None:
             loss, vals = _FusedLossFn.apply(*fused, None, fl)
@@ -259,6 +284,8 @@ def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, cos
             output_dic["cos"] = wvals[3]
         if wave is not None and wave[3] > 0:
             output_dic["si_sdr"] = wvals[4]
+        if stoi is not None:
+            output_dic["stoi"] = svals[1]
         return loss, output_dic
     den, l1 = denoise(out, clean, T)
     l1 = torch.abs(l1)
@@ -280,6 +307,11 @@ def loss_fn(net, X, ell_p, ell_p_lambda, stft_lambda, mrstftloss, pcen=None, cos
             si = cl.SISDRLoss(eps=si_sdr_eps)(den, clean)
             loss = loss + si * si_sdr_lambda
             output_dic["si_sdr"] = si.detach() * si_sdr_lambda
+    if stoi is not None:
+        from . import stoi_loss as stl
+        term = stl.STOILoss(extended=stoi[1])(den, clean)
+        loss = loss + term * stoi[0]
+        output_dic["stoi"] = term.detach() * stoi[0]
     return loss, output_dic
 
 
