@@ -152,8 +152,16 @@ int trunet_conv_wgrad(const trunet_wgrad_args* h_args, void* stream);
  * with e0 = seg.c0, e1 = seg.c1 of the segment (1, 0 for TRUNET_PRO_NONE), plus the BatchNorm-backward statistics
  * sum(g_s), sum(g_s * (zmask - e2)) of that source: partials[trunet_pw_bwd_nparts()][nchan][2].
  * Restrictions (else TRUNET_ENOTSUP, use trunet_conv_gemm + trunet_conv_wgrad): w.a_mode = TRUNET_PRO_BNBWD,
- * every segment pos_mul = pos_div = 1; M in {32,64,96,128} with nchan % 32 == 0 and sum nchan in {64,128,192} (MFMA kernel),
- * or M <= 8 with nchan % 8 == 0 (vector-ALU kernel for the thin last decoder layer). */
+ * every segment pos_mul = pos_div = 1, mode TRUNET_PRO_NONE or TRUNET_PRO_BNRELU and nchan % 32 == 0; M <= 32 (any M: the dz
+ * block is padded to one 32-row MFMA tile) with sum nchan == 128; M in {64, 96, 128} with sum nchan in {64, 128}; M == 64 also
+ * with sum nchan == 192, where no segment that reaches channels 128..191 may ask for statistics.  Every shape runs on
+ * pw_bwd_kernel (pw_bwd.hip); rows M .. of the padded dz block count as zero.  (M <= 8 with nchan % 8 == 0 runs on a
+ * vector-ALU kernel instead only when the environment has TRUNET_PWB_THIN_VALU=1, read once per process.)
+ * What a launch writes: every element (m < M, c < nchan) of the weight in EVERY partial image and elements b_off .. b_off +
+ * M - 1 of every bias row, whatever they held (no zero fill needed for this entry point), and nothing else of either;
+ * out[s] at every position q_s(p) some p reaches, all NP frames of it: dz is zero for frames >= N, so the padding columns
+ * receive 0, or with ACCUM the masked previous content; positions no p reaches keep their content.  The statistics leave
+ * frames >= N out. */
 enum { TRUNET_DG_STORE = 1,  /* write the data gradient of this segment to `out`          */
        TRUNET_DG_MASK = 2,   /* ReLU backward: multiply by [e0*zmask + e1 > 0]             */
        TRUNET_DG_STATS = 4,  /* BatchNorm-backward statistics of the source (needs MASK)   */

@@ -66,13 +66,14 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const trunet_wgrad_arg
             for (int j = 0; j < CB; ++j) acc[k][i][j] = 0.f;
     }
 
-    const int nch = a.NP / 256;
+    const int nch = (a.NP + 255) / 256;                 // NP is a multiple of 128: the last chunk may be half a chunk
     const int items = a.P * nch;
     const size_t dstr = (size_t)a.a_L * a.NP;           // dz channel stride
     for (int it = blockIdx.y * 4 + wave; it < items; it += gridDim.y * 4) {
         const int pi = it / nch;
         const int p = a.p_begin + pi;
         const int n = (it - pi * nch) * 256 + 4 * lane;
+        if (n >= a.NP) continue;                        // upper half of a half chunk (no cross-lane work in this loop)
         bool valid[NS];
         int qs[NS];
         bool any = bias_role;
