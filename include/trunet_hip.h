@@ -815,6 +815,10 @@ typedef struct {
 } trunet_bgemm_args;
 int trunet_bf16_gemm_nparts(void);
 int trunet_bf16_gemm(const trunet_bgemm_args* h_args, void* stream);
+/* the kernel instance trunet_bf16_gemm launches for these arguments (host only, no HIP call; the same argument checks and the
+ * same return codes as the launch): bgemm_kernel<nrt, pro, epi, full>, pro / epi = -1 for the instances that test modes and
+ * flags at run time.  full = 1 (no row or channel guards) needs M = 64 or 128 and every segment a multiple of 16 channels. */
+int trunet_bf16_gemm_plan(const trunet_bgemm_args* h_args, int* nrt, int* pro, int* epi, int* full);
 /* pack an fp32 weight into the A-fragment image: A(m, k) = W[(m + w_m_off)*ldw_m + c*ldw_c + h_seg_woff[s]] for segments of
  * h_seg_nchan[s] channels, each padded to whole k-steps of 16:
  * wfrag[((rt*nks_total + ks)*64 + lane)*8 + j] = A(32 rt + lane%32, 16 ks + 8 (lane/32) + j); returns nks_total (> 0) */

@@ -693,6 +693,127 @@ def test_bf16_kernel_name_mirror_and_precision_switch():
         TRUNet(precision="fp16")
 
 
+def _bgemm_plan_args(M, segs, epi):
+    """a valid trunet_bgemm_args block with dummy non-null pointers (the plan is host-only); segs: (nchan, mode) pairs"""
+    from tinyrecurrentunet_amd import _lib
+    a = _lib.BGemmArgs()
+    a.NP, a.N, a.P, a.p_begin, a.M, a.out_L, a.out_pos_off, a.nseg, a.epi, a.M_stat = 256, 200, 4, 0, M, 4, 0, len(segs), epi, M
+    for n in ("out", "wfrag", "bias", "zmask", "e0", "e1", "e2", "partials"):
+        setattr(a, n, 0x1000)
+    k0 = 0
+    for i, (nchan, mode) in enumerate(segs):
+        s = _lib.BSeg()
+        s.src0 = s.src1 = s.c0 = s.c1 = s.c2 = 0x2000
+        s.nchan, s.L, s.pos_mul, s.pos_off, s.pos_div, s.mode, s.kstep0 = nchan, 4, 1, 0, 1, mode, k0
+        k0 += ((nchan + 7) // 8 + 1) // 2
+        a.seg[i] = s
+    a.nks_total = k0
+    return a
+
+
+def _bgemm_plan(a):
+    import ctypes
+    from tinyrecurrentunet_amd import _lib
+    v = [ctypes.c_int(-9) for _ in range(4)]
+    rc = _lib.lib().trunet_bf16_gemm_plan(a, *[ctypes.byref(x) for x in v])
+    return rc, tuple(x.value for x in v)
+
+
+def test_bf16_gemm_plan_agrees_with_the_kernel_name_mirror_everywhere():
+    """trunet_bf16_gemm_plan reports the decision the launch itself takes (one function in csrc/bf16.hip);
+    engine_bf16._bgemm_name restates it for the profiles.  Swept over M x channel mixes x every (prologue, epilogue) pair the
+    entry point accepts: the two agree everywhere; FULL instances only at 64 and 128 rows (2 or 4 row tiles) -- 96 rows over
+    whole k-steps take the generic instance, whose waves clip their row tiles."""
+    from tinyrecurrentunet_amd import _lib
+    from tinyrecurrentunet_amd.engine_bf16 import _bgemm_name
+
+    class Sg:
+        def __init__(self, nchan, mode):
+            self.nchan, self.mode = nchan, mode
+    B, St, A, K, R, F = _lib.EPI_BIAS, _lib.EPI_STATS, _lib.EPI_ACCUM, _lib.EPI_MASK, _lib.EPI_RELU, _lib.EPI_F32OUT
+    NONE, BNRELU, BNBWD = _lib.PRO_NONE, _lib.PRO_BNRELU, _lib.PRO_BNBWD
+    mixes = {NONE: [[(64, NONE)], [(128, NONE)], [(4, NONE)] * 5, [(8, NONE)], [(24, NONE), (64, NONE)]],
+             BNRELU: [[(64, BNRELU)], [(64, BNRELU), (128, NONE)], [(32, BNRELU)] * 3, [(24, BNRELU), (64, NONE)],
+                      [(8, BNRELU)] * 5, [(64, BNRELU)] * 4 + [(128, NONE)]],
+             BNBWD: [[(64, BNBWD)], [(128, BNBWD)], [(8, BNBWD)], [(40, BNBWD)]]}
+    epis = [e for e in range(32)] + [F, B | F]                       # every combination of B, S, A, K, R; F32OUT alone / with B
+    seen, n = set(), 0
+    for M in (8, 32, 40, 64, 96, 128):
+        for pro, lists in mixes.items():
+            for segs in lists:
+                for epi in epis:
+                    rc, inst = _bgemm_plan(_bgemm_plan_args(M, segs, epi))
+                    assert rc == 0, (M, segs, epi, rc)
+                    rc2, inst2 = _bgemm_plan(_bgemm_plan_args(M, segs, epi | _lib.EPI_PREZERO))
+                    assert (rc2, inst2) == (rc, inst)                   # PREZERO is the host's business alone
+                    name = "bgemm_kernel<%d, %d, %d, %s>" % (inst[:3] + ("true" if inst[3] else "false",))
+                    assert _bgemm_name(M, [Sg(*s) for s in segs], epi) == name, (M, segs, epi, name)
+                    whole = M % 32 == 0 and all(c % 16 == 0 for c, _ in segs)
+                    assert not inst[3] or (whole and M in (64, 128)), (M, segs, epi, inst)
+                    assert inst[0] == (4 if inst[0] == 4 else (1 if M <= 32 else 2)) and (inst[0] != 4 or M == 128)
+                    assert (inst[1], inst[2]) in ((-1, -1), (pro, epi))
+                    seen.add(inst)
+                    n += 1
+    assert n == 6 * 15 * 34
+    assert len(seen) == 18, sorted(seen)                                # every instance of the dispatch
+    assert _bgemm_plan(_bgemm_plan_args(96, [(64, BNRELU)], B | St))[1] == (2, -1, -1, 0)
+    assert _bgemm_plan(_bgemm_plan_args(96, [(64, BNBWD)], K | St | A))[1] == (2, -1, -1, 0)
+    assert _bgemm_plan(_bgemm_plan_args(32, [(64, BNRELU)], B | St))[1] == (1, -1, -1, 0)
+
+
+def test_bf16_gemm_plan_checks_its_arguments_like_the_launch():
+    """host-only: TRUNET_EINVAL / TRUNET_ENOTSUP exactly where trunet_bf16_gemm returns them, before any HIP call, and the
+    four results untouched"""
+    import ctypes
+    from tinyrecurrentunet_amd import _lib
+    lib = _lib.lib()
+    EINVAL, ENOTSUP = _lib.TRUNET_EINVAL, _lib.TRUNET_ENOTSUP
+    B, St, K, F = _lib.EPI_BIAS, _lib.EPI_STATS, _lib.EPI_MASK, _lib.EPI_F32OUT
+    BNRELU, BNBWD = _lib.PRO_BNRELU, _lib.PRO_BNBWD
+    good = lambda **kw: _bgemm_plan_args(kw.pop("M", 64), kw.pop("segs", [(64, BNRELU)]), kw.pop("epi", B | St))
+    v = [ctypes.c_int(0) for _ in range(4)]
+    refs = [ctypes.byref(x) for x in v]
+    assert lib.trunet_bf16_gemm_plan(None, *refs) == EINVAL
+    for i in range(4):
+        assert lib.trunet_bf16_gemm_plan(good(), *[None if j == i else r for j, r in enumerate(refs)]) == EINVAL
+
+    def both(a, code, what):
+        assert _bgemm_plan(a) == (code, (-9, -9, -9, -9)), what
+        assert lib.trunet_bf16_gemm(a, None) == code, what             # refused on the host: no launch without a GPU
+
+    def changed(**kw):
+        a = good()
+        for k, val in kw.items():
+            setattr(a, k, val)
+        return a
+    for kw in (dict(out=None), dict(wfrag=None), dict(nseg=0), dict(nseg=6), dict(NP=200), dict(NP=0), dict(N=0), dict(N=257),
+               dict(P=0), dict(M=0), dict(out_L=0), dict(p_begin=-1), dict(out_pos_off=-1), dict(out_pos_off=1),
+               dict(partials=None), dict(M_stat=63), dict(bias=None), dict(nks_total=3)):
+        both(changed(**kw), EINVAL, kw)
+    for kw in (dict(zmask=None), dict(e0=None), dict(e1=None)):
+        a = good(epi=K | St)
+        setattr(a, *list(kw.items())[0])
+        both(a, EINVAL, kw)
+    a = good(epi=K | St)
+    a.e2 = None                                                        # optional
+    assert _bgemm_plan(a)[0] == 0
+    both(good(epi=B | F | St), EINVAL, "F32OUT with STATS")
+    a = good(M=128, epi=B | F)
+    a.m_out_off = -1
+    both(a, EINVAL, "m_out_off < 0")
+    both(changed(M=129, M_stat=129), ENOTSUP, "M = 129")
+    both(changed(nks_total=25), ENOTSUP, "25 k-steps")
+    both(changed(nks_total=0), ENOTSUP, "no k-steps")
+    both(good(segs=[(64, BNBWD), (64, BNRELU)], epi=K | St), ENOTSUP, "BatchNorm-backward pairs mixed with other segments")
+    for field, val in (("src0", None), ("nchan", 0), ("pos_div", 0), ("L", 0), ("mode", 3), ("kstep0", -1), ("c0", None)):
+        a = good()
+        setattr(a.seg[0], field, val)
+        both(a, EINVAL, field)
+    a = good(segs=[(64, BNBWD)], epi=K | St)
+    a.seg[0].src1 = None
+    both(a, EINVAL, "BNBWD without its second tensor")
+
+
 def test_checkpoint_round_trip_with_reference_layout(tmp_path):
     """train.py:155-162 checkpoints ({'iter','model_state_dict','optimizer_state_dict','training_time_seconds'} as
     '<iter>.pkl') load both ways between the reference layout (oracle modules = the reference's own block classes in the

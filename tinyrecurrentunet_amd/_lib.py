@@ -257,6 +257,7 @@ def _declare(L):
         "trunet_i8_mfma_probe": [p, p, p, p],
         "trunet_bf16_gemm_nparts": [],
         "trunet_bf16_gemm": [C.POINTER(BGemmArgs), p],
+        "trunet_bf16_gemm_plan": [C.POINTER(BGemmArgs)] + [C.POINTER(C.c_int)] * 4,
         "trunet_bf16_pack_weight": [p, p, i, i, i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), p],
         "trunet_bf16_pack_weights_batch": [p, i, i, p],
         "trunet_bf16_wgrad": [C.POINTER(BWgradArgs), p],

@@ -212,7 +212,9 @@ __global__ __launch_bounds__(256, 2) void bgemm_kernel(const trunet_bgemm_args a
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int m0 = (rt0 + t) * 32 + 8 * g + 4 * h;          // first of this lane's 4 rows
-                if (!FULL && m0 >= a.M) continue;
+                // an octet wholly past M is not part of `out`; inside the last octet the half-wave whose 4 rows are all padding
+                // (M % 8 in 1 .. 4) still stores them, as zeros
+                if (!FULL && m0 - 4 * h >= a.M) continue;
                 asm volatile("" ::: "memory");
                 f32x4 bv = {0.f, 0.f, 0.f, 0.f}, e0v = bv, e1v = bv, muv = bv;
                 if (has(TRUNET_EPI_BIAS)) bv = *(const f32x4*)(Ep + m0);
@@ -921,12 +923,8 @@ static bool bseg_ok(const trunet_bseg& sg) {
     return true;
 }
 
-extern "C" int trunet_bf16_gemm(const trunet_bgemm_args* h_in, void* stream) {
-    if (!h_in) return TRUNET_EINVAL;
-    trunet_bgemm_args hcopy = *h_in;                 // the template dispatch below compares `epi` exactly
-    const bool prezero = (hcopy.epi & TRUNET_EPI_PREZERO) != 0;
-    hcopy.epi &= ~TRUNET_EPI_PREZERO;
-    const trunet_bgemm_args* h = &hcopy;
+// Arguments of trunet_bf16_gemm the host can judge (`h` with TRUNET_EPI_PREZERO already taken out of `epi`)
+static int bgemm_check(const trunet_bgemm_args* h) {
     if (!h->out || !h->wfrag || h->nseg < 1 || h->nseg > TRUNET_MAX_SEG) return TRUNET_EINVAL;
     if (h->NP <= 0 || (h->NP % 64) != 0 || h->N <= 0 || h->N > h->NP || h->P <= 0 || h->M <= 0) return TRUNET_EINVAL;
     if (h->M > 128 || h->nks_total <= 0 || h->nks_total > BG_MAXKS) return TRUNET_ENOTSUP;
@@ -941,65 +939,118 @@ extern "C" int trunet_bf16_gemm(const trunet_bgemm_args* h_in, void* stream) {
         if (!bseg_ok(sg) || sg.kstep0 < 0) return TRUNET_EINVAL;
         if (sg.kstep0 + (((sg.nchan + 7) / 8 + 1) / 2) > h->nks_total) return TRUNET_EINVAL;
     }
+    return TRUNET_OK;
+}
+
+// The template instance bgemm_kernel<nrt, pro, epi, full> of a launch: THE decision, shared by trunet_bf16_gemm and
+// trunet_bf16_gemm_plan.  TRUNET_ENOTSUP for BatchNorm-backward pairs mixed with other segments.
+struct BgPlan { int nrt, pro, epi; bool full; };
+static int bgemm_plan(const trunet_bgemm_args* h, BgPlan* pl) {
+    const int nrt_all = (h->M + 31) / 32;
+    // prologue class of the launch: BatchNorm-backward pairs, BN+ReLU (plain segments in it must be post-ReLU sources:
+    // they get identity coefficients), or plain
+    int pro = TRUNET_PRO_NONE;
+    // whole: whole row tiles and whole 16-channel k-steps, nothing for a row or channel guard to do
+    bool whole = (h->M % 32) == 0, mixed = false;
+    for (int s = 0; s < h->nseg; ++s) {
+        const int m = h->seg[s].mode;
+        if (m == TRUNET_PRO_BNBWD) pro = TRUNET_PRO_BNBWD;
+        else if (m == TRUNET_PRO_BNRELU && pro != TRUNET_PRO_BNBWD) pro = TRUNET_PRO_BNRELU;
+        whole = whole && (h->seg[s].nchan % 16) == 0;
+    }
+    for (int s = 0; s < h->nseg; ++s) mixed = mixed || (pro == TRUNET_PRO_BNBWD && h->seg[s].mode != TRUNET_PRO_BNBWD);
+    if (mixed) return TRUNET_ENOTSUP;
+    // FULL instances have no guards and give EVERY wave NRT row tiles, so the row tiles must divide among the waves of a
+    // tile: 2 (one wave) or 4 (one wave, or two waves with two each).  With 3 (M = 96) the second wave of a split tile would
+    // compute a fourth row tile that does not exist -- A fragments past the LDS image, stores past the tensor: such a launch
+    // takes the generic instance, whose waves clip their row tiles (nrt = min(NRT, nrt_all - rt0))
+    const bool full = whole && (nrt_all == 2 || nrt_all == 4);
+    constexpr int B = TRUNET_EPI_BIAS, S = TRUNET_EPI_STATS, A = TRUNET_EPI_ACCUM, K = TRUNET_EPI_MASK, R = TRUNET_EPI_RELU,
+                  F = TRUNET_EPI_F32OUT;
+    const int epi = h->epi;
+    auto is = [&](int p, int e) { return pro == p && epi == e; };
+    pl->pro = pro; pl->epi = epi;
+    if (full) {                             // the hot launches of the training step
+        pl->full = true;
+        // 128 rows forward: ONE wave per tile with all four row tiles (the split form runs the prologue twice): -0.15 ms
+        pl->nrt = 4;
+        if (nrt_all == 4 && (is(TRUNET_PRO_BNRELU, B | S) || is(TRUNET_PRO_NONE, B | S) || is(TRUNET_PRO_BNRELU, B | F))) return TRUNET_OK;
+        pl->nrt = 2;
+        if (is(TRUNET_PRO_BNRELU, B | S) || is(TRUNET_PRO_NONE, B | S) || is(TRUNET_PRO_NONE, K | S) || is(TRUNET_PRO_BNBWD, K | S) ||
+            is(TRUNET_PRO_BNBWD, K | S | A) || is(TRUNET_PRO_BNBWD, K | A) || is(TRUNET_PRO_BNBWD, 0))
+            return TRUNET_OK;
+    } else if (!whole) {
+        // the thin layers of the training step (first conv 4 -> 64, decoder.5: 128 -> 8 and 8 -> 8): channel guards stay, the
+        // prologue / epilogue are compile-time like above
+        pl->full = false;
+        pl->nrt = nrt_all == 1 ? 1 : 2;
+        if (nrt_all == 1 ? (is(TRUNET_PRO_BNRELU, B | S) || is(TRUNET_PRO_BNRELU, B) || is(TRUNET_PRO_NONE, K | S))
+                         : (is(TRUNET_PRO_NONE, B | R) || is(TRUNET_PRO_BNBWD, K | S) || is(TRUNET_PRO_BNBWD, 0)))
+            return TRUNET_OK;
+    }
+    // everything else (eval-mode forwards, other shapes): flags and modes tested at run time
+    pl->nrt = nrt_all == 1 ? 1 : 2; pl->pro = -1; pl->epi = -1; pl->full = false;
+    return TRUNET_OK;
+}
+
+extern "C" int trunet_bf16_gemm_plan(const trunet_bgemm_args* h_in, int* nrt, int* pro, int* epi, int* full) {
+    if (!h_in || !nrt || !pro || !epi || !full) return TRUNET_EINVAL;
+    trunet_bgemm_args hcopy = *h_in;
+    hcopy.epi &= ~TRUNET_EPI_PREZERO;
+    BgPlan pl;
+    int rc = bgemm_check(&hcopy);
+    if (rc == TRUNET_OK) rc = bgemm_plan(&hcopy, &pl);
+    if (rc != TRUNET_OK) return rc;
+    *nrt = pl.nrt; *pro = pl.pro; *epi = pl.epi; *full = pl.full ? 1 : 0;
+    return TRUNET_OK;
+}
+
+extern "C" int trunet_bf16_gemm(const trunet_bgemm_args* h_in, void* stream) {
+    if (!h_in) return TRUNET_EINVAL;
+    trunet_bgemm_args hcopy = *h_in;                 // the plan compares `epi` exactly
+    const bool prezero = (hcopy.epi & TRUNET_EPI_PREZERO) != 0;
+    hcopy.epi &= ~TRUNET_EPI_PREZERO;
+    const trunet_bgemm_args* h = &hcopy;
+    BgPlan pl;
+    int rc = bgemm_check(h);
+    if (rc == TRUNET_OK) rc = bgemm_plan(h, &pl);
+    if (rc != TRUNET_OK) return rc;
     if ((h->epi & TRUNET_EPI_STATS) && !prezero) {
         if (hipMemsetAsync(h->partials, 0, (size_t)trunet_bf16_gemm_nparts() * h->M_stat * 2 * sizeof(float), ST) != hipSuccess)
             return TRUNET_ELAUNCH;
     }
     const int nrt_all = (h->M + 31) / 32;
     const size_t lds = (size_t)nrt_all * h->nks_total * 64 * 16 + (size_t)h->nks_total * 2 * 3 * 8 * sizeof(float) + 4 * 128 * sizeof(float);
-    // prologue class of the launch: BatchNorm-backward pairs, BN+ReLU (plain segments in it must be post-ReLU sources:
-    // they get identity coefficients), or plain
-    int pro = TRUNET_PRO_NONE;
-    bool full = (h->M % 32) == 0, mixed = false;
-    for (int s = 0; s < h->nseg; ++s) {
-        const int m = h->seg[s].mode;
-        if (m == TRUNET_PRO_BNBWD) pro = TRUNET_PRO_BNBWD;
-        else if (m == TRUNET_PRO_BNRELU && pro != TRUNET_PRO_BNBWD) pro = TRUNET_PRO_BNRELU;
-        full = full && (h->seg[s].nchan % 16) == 0;
-    }
-    for (int s = 0; s < h->nseg; ++s) mixed = mixed || (pro == TRUNET_PRO_BNBWD && h->seg[s].mode != TRUNET_PRO_BNBWD);
-    if (mixed) return TRUNET_ENOTSUP;
 #define BG_LAUNCH(NRT_, PRO_, EPI_, FULL_)                                                                                          \
-    do {                                                                                                                            \
+    if (pl.nrt == NRT_ && pl.pro == PRO_ && pl.epi == (EPI_) && pl.full == FULL_) {                                                 \
         if (hipFuncSetAttribute((const void*)bgemm_kernel<NRT_, PRO_, EPI_, FULL_>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
                                 (int)lds) != hipSuccess)                                                                            \
             return TRUNET_ELAUNCH;                                                                                                  \
         hipLaunchKernelGGL((bgemm_kernel<NRT_, PRO_, EPI_, FULL_>), dim3(BG_GRID), dim3(256), lds, ST, *h);                         \
         return trunet_launch_status();                                                                                              \
-    } while (0)
-    constexpr int B = TRUNET_EPI_BIAS, S = TRUNET_EPI_STATS, A = TRUNET_EPI_ACCUM, K = TRUNET_EPI_MASK;
-    if (full && nrt_all >= 2) {             // the hot launches of the training step
-        // 128 rows forward: ONE wave per tile with all four row tiles (the split form runs the prologue twice): -0.15 ms
-        if (pro == TRUNET_PRO_BNRELU && h->epi == (B | S) && nrt_all == 4) BG_LAUNCH(4, TRUNET_PRO_BNRELU, B | S, true);
-        if (pro == TRUNET_PRO_NONE && h->epi == (B | S) && nrt_all == 4) BG_LAUNCH(4, TRUNET_PRO_NONE, B | S, true);
-        if (pro == TRUNET_PRO_BNRELU && h->epi == (B | S)) BG_LAUNCH(2, TRUNET_PRO_BNRELU, B | S, true);
-        if (pro == TRUNET_PRO_NONE && h->epi == (B | S)) BG_LAUNCH(2, TRUNET_PRO_NONE, B | S, true);
-        if (pro == TRUNET_PRO_BNRELU && h->epi == (B | TRUNET_EPI_F32OUT) && nrt_all == 4)
-            BG_LAUNCH(4, TRUNET_PRO_BNRELU, B | TRUNET_EPI_F32OUT, true);
-        if (pro == TRUNET_PRO_NONE && h->epi == (K | S)) BG_LAUNCH(2, TRUNET_PRO_NONE, K | S, true);
-        if (pro == TRUNET_PRO_BNBWD && h->epi == (K | S)) BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | S, true);
-        if (pro == TRUNET_PRO_BNBWD && h->epi == (K | S | A)) BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | S | A, true);
-        if (pro == TRUNET_PRO_BNBWD && h->epi == (K | A)) BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | A, true);
-        if (pro == TRUNET_PRO_BNBWD && h->epi == 0) BG_LAUNCH(2, TRUNET_PRO_BNBWD, 0, true);
     }
-    // the thin layers of the training step (first conv 4 -> 64, decoder.5: 128 -> 8 and 8 -> 8): channel guards stay, the
-    // prologue / epilogue are compile-time like above
-    constexpr int R = TRUNET_EPI_RELU;
-    if (!full) {
-        if (nrt_all == 1) {
-            if (pro == TRUNET_PRO_BNRELU && h->epi == (B | S)) BG_LAUNCH(1, TRUNET_PRO_BNRELU, B | S, false);
-            if (pro == TRUNET_PRO_BNRELU && h->epi == B) BG_LAUNCH(1, TRUNET_PRO_BNRELU, B, false);
-            if (pro == TRUNET_PRO_NONE && h->epi == (K | S)) BG_LAUNCH(1, TRUNET_PRO_NONE, K | S, false);
-        } else {
-            if (pro == TRUNET_PRO_NONE && h->epi == (B | R)) BG_LAUNCH(2, TRUNET_PRO_NONE, B | R, false);
-            if (pro == TRUNET_PRO_BNBWD && h->epi == (K | S)) BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | S, false);
-            if (pro == TRUNET_PRO_BNBWD && h->epi == 0) BG_LAUNCH(2, TRUNET_PRO_BNBWD, 0, false);
-        }
-    }
-    // everything else (eval-mode forwards, other shapes): flags and modes tested at run time
-    if (nrt_all == 1) BG_LAUNCH(1, -1, -1, false);
-    BG_LAUNCH(2, -1, -1, false);
+    constexpr int B = TRUNET_EPI_BIAS, S = TRUNET_EPI_STATS, A = TRUNET_EPI_ACCUM, K = TRUNET_EPI_MASK, R = TRUNET_EPI_RELU;
+    // the 20 instances: one line each, picked by the plan
+    BG_LAUNCH(4, TRUNET_PRO_BNRELU, B | S, true)
+    BG_LAUNCH(4, TRUNET_PRO_NONE, B | S, true)
+    BG_LAUNCH(4, TRUNET_PRO_BNRELU, B | TRUNET_EPI_F32OUT, true)
+    BG_LAUNCH(2, TRUNET_PRO_BNRELU, B | S, true)
+    BG_LAUNCH(2, TRUNET_PRO_NONE, B | S, true)
+    BG_LAUNCH(2, TRUNET_PRO_NONE, K | S, true)
+    BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | S, true)
+    BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | S | A, true)
+    BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | A, true)
+    BG_LAUNCH(2, TRUNET_PRO_BNBWD, 0, true)
+    BG_LAUNCH(1, TRUNET_PRO_BNRELU, B | S, false)
+    BG_LAUNCH(1, TRUNET_PRO_BNRELU, B, false)
+    BG_LAUNCH(1, TRUNET_PRO_NONE, K | S, false)
+    BG_LAUNCH(2, TRUNET_PRO_NONE, B | R, false)
+    BG_LAUNCH(2, TRUNET_PRO_BNBWD, K | S, false)
+    BG_LAUNCH(2, TRUNET_PRO_BNBWD, 0, false)
+    BG_LAUNCH(1, -1, -1, false)
+    BG_LAUNCH(2, -1, -1, false)
 #undef BG_LAUNCH
+    return TRUNET_ENOTSUP;                  // a plan without an instance: unreachable while the list above is complete
 }
 
 extern "C" int trunet_bf16_pack_weight(const float* W, void* wfrag, int M, int ldw_m, int ldw_c, int w_m_off, int nseg,

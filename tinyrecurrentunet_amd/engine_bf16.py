@@ -94,18 +94,19 @@ def _bgemm_name(M, segs, epi):
             pro = PRO_BNBWD
         elif s.mode == PRO_BNRELU and pro != PRO_BNBWD:
             pro = PRO_BNRELU
-    full = M % 32 == 0 and all(s.nchan % 16 == 0 for s in segs)
+    whole = M % 32 == 0 and all(s.nchan % 16 == 0 for s in segs)
+    full = whole and M in (64, 128)         # 2 or 4 row tiles: 96 rows do not divide among the waves of a split tile
     B, S, A, K = EPI_BIAS, EPI_STATS, EPI_ACCUM, EPI_MASK
     hot = {(PRO_BNRELU, B | S), (PRO_NONE, B | S), (PRO_BNBWD, K | S), (PRO_BNBWD, K | S | A), (PRO_BNBWD, K | A),
            (PRO_BNBWD, 0), (PRO_NONE, K | S)}
     if full and M == 128 and (pro, epi) in {(PRO_BNRELU, B | S), (PRO_NONE, B | S), (PRO_BNRELU, B | EPI_F32OUT)}:
         return "bgemm_kernel<4, %d, %d, true>" % (pro, epi)
-    if full and M > 32 and (pro, epi) in hot:
+    if full and (pro, epi) in hot:
         return "bgemm_kernel<2, %d, %d, true>" % (pro, epi)
     R = EPI_RELU
     thin1 = {(PRO_BNRELU, B | S), (PRO_BNRELU, B), (PRO_NONE, K | S)}
     thin2 = {(PRO_NONE, B | R), (PRO_BNBWD, K | S), (PRO_BNBWD, 0)}
-    if not full and (pro, epi) in (thin1 if M <= 32 else thin2):
+    if not whole and (pro, epi) in (thin1 if M <= 32 else thin2):
         return "bgemm_kernel<%d, %d, %d, false>" % (1 if M <= 32 else 2, pro, epi)
     return "bgemm_kernel<%d, -1, -1, false>" % (1 if M <= 32 else 2)
 
