@@ -566,6 +566,45 @@ int trunet_highband_join(const float* up_y, const float* up_x, const float* x, c
                          const int64_t* sample_off, const int64_t* up_off, const int64_t* frame_off, int B,
                          int64_t total_samples, int64_t total_up, int64_t total_frames, int pd, int qd, int mode,
                          void* stream);
+/* trunet_stream_highband_* (stream_highband.py, StreamPool(highband=)): the same band for sessions that
+ * arrive in packets.  Per slot: x_line (slots, xcap) the samples at fs fed and not yet returned; lo_line (slots,
+ * TRUNET_SHB_LO_LINE) the samples of lo whose ys16 has not come back; "follow" only: halo (slots, 62, 2) the last 62 samples
+ * of lo and ys16 interleaved, estate (slots, 3, 2) the last three block energies (E_x, E_y), gstate (slots, 2) the last two
+ * block gains.  Per call: packet (n_packet) the packets at fs and x16 (n_x16) their down-resampled samples, back to back;
+ * paired, ys16 (n_paired): the lo that pairs with the call's ys16, and that ys16; up_y, up_x, out (n_up); eline (n_blocks +
+ * 3 n_sess, 2) and gline (n_blocks + 2 n_sess): per record the slot's last three energies / two gains, then the call's new
+ * blocks.  plan: DEVICE array (n_sess, TRUNET_SHB_INTS) int64, one record per listed session, distinct slots:
+ *   [0] slot   [1] samples in its x line   [2] offset and [3] length of its packet   [4] offset of its outputs in up_y, up_x
+ *   and out   [5] outputs to write (<= [1] + [3])   [6] samples in its lo line   [7] offset and [8] length of its new x16
+ *   [9] offset and [10] length pn of its paired samples (<= [6] + [8])   [11] outputs it was given before the call
+ *   [12] hop blocks complete before the call   [13] new blocks bn: pn / 128, or ceil(pn / 128) when closing   [14] its first
+ *   tile of the join (TRUNET_SHB_TILE outputs each)   [15] closing: nothing of the slot is kept   [16] its first tile of the
+ *   pairing   [17] the sum of [13] over the records before it.
+ * pair: paired <- the first pn samples of [lo line | x16].  gains: eline, then gline (two launches).  join: out[n] =
+ * up_y[n] + G[n] (x[n] - up_x[n]) with x from [x line | packet]; TRUNET_HB_KEEP: G = 1 and gline may be NULL;
+ * TRUNET_HB_FOLLOW: G[n] = ((D - c) g_c[max(j - 1, 0)] + c g_c[j]) / D, s = ([11] + n) pd, D = 128 qd, j = s / D, c = s % D.
+ * commit, after them on the same stream: the lines drop what was consumed and take what came, and the "follow" state moves
+ * on.  pair, gains and join only read the per-slot state.  TRUNET_EINVAL without a launch for anything the host can see; a
+ * record that leaves the extents passed in is skipped by every kernel. */
+#define TRUNET_SHB_INTS 18
+#define TRUNET_SHB_LO_LINE 512
+#define TRUNET_SHB_MAX_X_LINE 4096
+#define TRUNET_SHB_TILE 1024
+int trunet_stream_highband_pair(const float* lo_line, const float* x16, float* paired, const int64_t* plan, int n_sess,
+                                int slots, int xcap, int64_t n_packet, int64_t n_up, int64_t n_x16, int64_t n_paired,
+                                int64_t n_blocks, int64_t n_tiles, void* stream);
+int trunet_stream_highband_gains(const float* paired, const float* ys16, const float* halo, const float* estate,
+                                 const float* gstate, const float* hp, float* eline, float* gline, const int64_t* plan,
+                                 int n_sess, int slots, int xcap, int64_t n_packet, int64_t n_up, int64_t n_x16,
+                                 int64_t n_paired, int64_t n_blocks, float g_min, void* stream);
+int trunet_stream_highband_join(const float* up_y, const float* up_x, const float* x_line, const float* packet,
+                                const float* gline, float* out, const int64_t* plan, int n_sess, int slots, int xcap,
+                                int64_t n_packet, int64_t n_up, int64_t n_x16, int64_t n_paired, int64_t n_blocks,
+                                int64_t n_tiles, int pd, int qd, int mode, void* stream);
+int trunet_stream_highband_commit(float* x_line, const float* packet, float* lo_line, const float* x16, float* halo,
+                                  const float* paired, const float* ys16, float* estate, const float* eline, float* gstate,
+                                  const float* gline, const int64_t* plan, int n_sess, int slots, int xcap, int64_t n_packet,
+                                  int64_t n_up, int64_t n_x16, int64_t n_paired, int64_t n_blocks, int mode, void* stream);
 size_t trunet_stoi_workspace_bytes(int B, int64_t total_frames, int64_t total_segments);
 int trunet_stoi_ragged(const float* sig, const int64_t* sig_off, const int64_t* frame_off, const int64_t* seg_off,
                        const int64_t* chunk_off, const float* window, const int* band_edges, const float* tw512,

@@ -223,6 +223,10 @@ def _declare(L):
         "trunet_resample_stream_commit": [p, p, p, i, i, i, i, i, i, i64, p],
         "trunet_highband_gains": [p, p, p, p, p, p, p, i, i64, i64, f, p],
         "trunet_highband_join": [p, p, p, p, p, p, p, p, i, i64, i64, i64, i, i, i, p],
+        "trunet_stream_highband_pair": [p, p, p, p, i, i, i, i64, i64, i64, i64, i64, i64, p],
+        "trunet_stream_highband_gains": [p, p, p, p, p, p, p, p, p, i, i, i, i64, i64, i64, i64, i64, f, p],
+        "trunet_stream_highband_join": [p, p, p, p, p, p, p, i, i, i, i64, i64, i64, i64, i64, i64, i, i, i, p],
+        "trunet_stream_highband_commit": [p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i64, i64, i64, i64, i64, i, p],
         "trunet_stoi_workspace_bytes": [i, i64, i64],
         "trunet_stoi_ragged": [p] * 12 + [i, i64, i64, i64, i64, p],
         "trunet_si_sdr_ragged": [p, p, p, p, p, p, i, i64, i64, p],

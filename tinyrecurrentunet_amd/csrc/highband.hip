@@ -19,6 +19,7 @@
 // is off[b], owns the grid slots [off[b] / W + b, off[b + 1] / W + b + 1), at least ceil((off[b + 1] - off[b]) / W) of
 // them; a slot past the utterance's last tile returns.
 #include "common.hpp"
+#include "highband_mix.hpp"
 
 namespace {
 
@@ -136,13 +137,6 @@ __global__ __launch_bounds__(256) void highband_gain_kernel(const f32x2* __restr
     g[f] = fminf(fmaxf(r, g_min), 1.f);
 }
 
-// the one expression of the join: up_y + G (x - up_x); G = 1 adds the band as it is
-template <bool FOLLOW>
-__device__ __forceinline__ float hb_mix(float upy, float upx, float x, float G) {
-    const float hb = x - upx;
-    return FOLLOW ? fmaf(G, hb, upy) : upy + hb;
-}
-
 // the gains of the samples n, n + 1, ..: c = (n pd) % D and t0 = (n pd) / D walk with the sample
 struct hb_walk {
     const float* g;          // the utterance's T frame gains
@@ -151,9 +145,8 @@ struct hb_walk {
     unsigned c, pd, D;
     __device__ __forceinline__ float next() {
         const int ta = t0 < last ? t0 : last, tb = ta < last ? ta + 1 : last;
-        // (1 - al) g[ta] + al g[tb], al = c / D, as (g[ta] (D - c) + g[tb] c) / D: c and D - c are exact in fp32, so G
-        // carries three roundings relative to itself however far apart the two gains lie
-        const float G = fmaf(g[tb], (float)c, g[ta] * (float)(D - c)) / (float)D;
+        // (1 - al) g[ta] + al g[tb], al = c / D, as (g[ta] (D - c) + g[tb] c) / D (highband_mix.hpp)
+        const float G = hb_lerp(g[ta], g[tb], c, D);
         c += pd;
         if (c >= D) {        // pd < D: at most one frame per sample
             c -= D;

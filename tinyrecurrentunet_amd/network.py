@@ -303,7 +303,8 @@ class TRUNet(nn.Module):
     def stream_pool(self, slots, **kw):
         """A ``streaming.StreamPool`` of ``slots`` independent streaming sessions on this network (eval mode): sessions open,
         step, pause and close on their own, at any length from 257 samples; see the class for ``tgru`` / ``beta`` / ``int8`` /
-        ``fs`` (packets at 8 to 96 kHz, resampled on the GPU)."""
+        ``fs`` (packets at 8 to 96 kHz, resampled on the GPU) / ``highband`` (above 16 kHz: the band above 8 kHz kept or
+        following the network's suppression)."""
         from .streaming import StreamPool
         return StreamPool(self, slots, **kw)
 

@@ -369,7 +369,8 @@ class SlotAllocator:
 class StreamPool:
     """A fixed number of independent streaming sessions on the single-launch forward.
 
-        pool = StreamPool(net, slots, tgru=None, beta=0.5, int8=False, fs=16000)   # net in eval mode on the GPU; tgru None: net.use_tgru
+        pool = StreamPool(net, slots, tgru=None, beta=0.5, int8=False, fs=16000,   # net in eval mode on the GPU; tgru None: net.use_tgru
+                          highband="drop", highband_floor_db=-30.0)
         ids = pool.open(n)                      # n free slot ids
         out, valid = pool.step(chunks, ids)     # chunks (n, 128) fp32 cuda; ids: n distinct open slots
         rest = pool.close(ids, tails)           # list of 1-D tensors; tails[i]: the 0..127 last samples of session i, or None
@@ -426,16 +427,38 @@ class StreamPool:
     call-mates stay open and unchanged.  Each resampler adds a look-ahead of 16 samples at the lower of its two rates (1
     ms each way at 48 kHz) to the four hops of the 16 kHz path.  ``step`` and ``close`` with a non-empty tail take 16
     kHz hops and are a ValueError at another rate; ``pending`` and ``hops`` keep their 16 kHz meaning; ``open`` and
-    ``abort`` reset both resamplers' counters of the slot.  The band above 8 kHz is not restored.  With the default ``fs``
-    nothing changes.  ``AudioStream`` stays at 16 kHz."""
+    ``abort`` reset both resamplers' counters of the slot.  With the default ``fs`` nothing changes.  ``AudioStream`` stays
+    at 16 kHz.
 
-    def __init__(self, net, slots, tgru=None, beta=0.5, int8=False, fs=SAMPLE_RATE):
+    ``highband`` (keyword only; ``pool.highband``, ``pool.highband_floor_db``): what becomes of the band above 8 kHz when
+    ``fs`` > 16 kHz.  ``"drop"``, the default: the pool above, bit for bit, with no further allocation or
+    launch; the two low-passes leave nothing above 0.94 of 8 kHz.  ``"keep"``: out = up_y + (x - up_x), with up_x the
+    session's own down-resampled samples resampled back; however the packets are cut, ``feed`` ... ``close`` is bit for bit
+    ``highband.rejoin([x], [lo], [ys16], fs, "keep")[0]``.  ``"follow"``: out[n] = up_y[n] + G[n] (x[n] - up_x[n]) with a
+    CAUSAL gain, the square root of the ratio of the energies of the enhanced and the incoming 16 kHz signal above 4 kHz
+    (63-tap high-pass, 2 ms late) over the four hops that end where sample n is emitted, clamped to
+    [10^(highband_floor_db / 20), 1] and interpolated from hop to hop.  That gain trails the suppression it follows by about
+    two hops plus the filter's 2 ms; it is a definition of its own (``stream_highband``'s docstring, pinned in float64 by
+    tests/stream_highband_ref.py), not the offline ``"follow"``, which looks two hops ahead and would cost 32 ms.  Neither
+    mode adds latency: ``feed`` returns, call by call, the sample counts of ``"drop"``.  Per slot the pool then also keeps
+    the samples at ``fs`` fed and not yet returned (at most 543 fs / 16000), the samples at 16 kHz that the network has not
+    returned (at most 511), a third stream resampler plane and, for ``"follow"``, 62 samples of either 16 kHz signal, three
+    block energies and two gains; ``open`` and ``abort`` reset their counters, host work only.  A mode outside
+    ``highband.MODES`` and a floor outside (-inf, 0] are a ValueError before anything reaches the device; at ``fs`` <= 16 kHz
+    the arguments are validated and the pool is that of ``"drop"``; a rate whose per-slot line cannot be bounded inside
+    4096 samples (above 120 kHz) is refused at construction.  ``step`` and ``close`` with a tail stay a ValueError at these
+    rates."""
+
+    def __init__(self, net, slots, tgru=None, beta=0.5, int8=False, fs=SAMPLE_RATE, *, highband="drop",
+                 highband_floor_db=-30.0):
+        from . import highband as HB
+        HB.check_args(highband, highband_floor_db)               # before anything touches the network or the device
         if net.training:
             raise L.TrunetHipError("StreamPool is an inference path: call net.eval() first")
         dev = next(net.parameters()).device
         if dev.type != "cuda":
             raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: the network sits on %s" % dev)
-        self._host_init(slots, fs, dev)
+        self._host_init(slots, fs, dev, highband, highband_floor_db)
         self.tgru = bool(net.use_tgru if tgru is None else tgru)
         self.net, self.beta, self.dev = net, float(beta), dev
         self.C = net.encoder[0].StandardConv1d[0].in_channels
@@ -457,20 +480,26 @@ class StreamPool:
         self.fifo = z(S, HOP)                                    # feed(): the 0..127 samples that wait for their hop to fill
         self.tw = L.twiddles(N_FFT, dev)
 
-    def _host_init(self, slots, fs, dev):
+    def _host_init(self, slots, fs, dev, highband="drop", highband_floor_db=-30.0):
         """the host side of a pool: the slot allocator, the per-slot counters and, at another rate than 16 kHz, the two
-        stream resamplers (whose device buffers come with their first launch).  No device work."""
+        stream resamplers (whose device buffers come with their first launch); above 16 kHz with ``highband`` "keep" or
+        "follow", the state that carries the band above 8 kHz.  No device work."""
+        from . import highband as HB
         from . import resample as R
+        self.highband, self.highband_floor_db = HB.check_args(highband, highband_floor_db)
         R.ratio(fs, SAMPLE_RATE)
         self._alloc = SlotAllocator(slots)
         S = self._alloc.capacity
         self.fs, self.dev = int(fs), dev
         self._hops = np.zeros(S, dtype=np.int64)
         self._pend = np.zeros(S, dtype=np.int64)                 # samples in the FIFO, per slot
-        self._down = self._up = None
+        self._down = self._up = self._hb = None
         if self.fs != SAMPLE_RATE:
             self._down = R.StreamResampler(self.fs, SAMPLE_RATE, S, dev)
             self._up = R.StreamResampler(SAMPLE_RATE, self.fs, S, dev)
+        if self.fs > SAMPLE_RATE and self.highband != "drop":    # at or below 16 kHz nothing lies above the network's band
+            from .stream_highband import StreamHighband
+            self._hb = StreamHighband(self.fs, S, self.highband, self.highband_floor_db, dev)
 
     # ---- host-side bookkeeping
     @property
@@ -511,6 +540,8 @@ class StreamPool:
         if self._down is not None and len(ids):
             self._down.reset(ids)
             self._up.reset(ids)
+            if self._hb is not None:
+                self._hb.reset(ids)
 
     def _ids(self, ids):
         """-> int64 array of distinct open slots; raises otherwise"""
@@ -679,18 +710,49 @@ class StreamPool:
         return out
 
     # ---- another rate than 16 kHz: a stream resampler on either side of the 16 kHz pass
-    def _feed_at(self, parts, lens, ids):
-        """``feed`` at ``fs``: down-resample, the 16 kHz pass on what became ready, up-resample what it returned.  The three
-        plans are made before the first launch, so a refusal leaves every session as it was."""
-        down, up = self._down, self._up
+    def _plan_feed_at(self, lens, ids):
+        """the plans of a ``feed`` at ``fs``, host only: down, 16 kHz, up and (or None) the band above 8 kHz"""
+        down, up, hb = self._down, self._up, self._hb
         pd = down.plan(lens, ids)
         p16 = plan_feed(self._hops, self._pend, np.asarray(pd.lengths, dtype=np.int64), ids)
         pu = up.plan(np.asarray(p16.lengths, dtype=np.int64), ids)
+        ph = None if hb is None else hb.plan(ids, lens, pd.lengths, p16.lengths, pu, up._emit[ids])
+        return pd, p16, pu, ph
+
+    def _plan_close_at(self, ids):
+        """the plans of a ``close`` at ``fs``, host only -> (down, 16 kHz feed, 16 kHz close, up, band above 8 kHz or None,
+        samples each session still gets); ValueError for a session below 257 samples at 16 kHz"""
+        down, up, hb = self._down, self._up, self._hb
+        fed = down._recv[ids].copy()
+        pd = down.plan(np.zeros(len(ids), dtype=np.int64), ids, True)
+        L16 = HOP * self._hops[ids] + self._pend[ids] + np.asarray(pd.lengths, dtype=np.int64)     # = ceil(fed p / q)
+        if (L16 < MIN_SAMPLES).any():
+            i = int(np.argmax(L16 < MIN_SAMPLES))
+            raise ValueError("session %d has %d samples at %d Hz, %d at %d Hz; at least %d are needed there (reflect padding "
+                             "of the first frame)" % (ids[i], fed[i], self.fs, L16[i], SAMPLE_RATE, MIN_SAMPLES))
+        p16 = plan_feed(self._hops, self._pend, np.asarray(pd.lengths, dtype=np.int64), ids)
+        pc = plan_close(p16.hops, p16.pending, ids)
+        both = np.asarray(p16.lengths, dtype=np.int64) + np.asarray(pc.lengths, dtype=np.int64)
+        pu = up.plan(both, ids, True)
+        owed = np.minimum(np.asarray(pu.lengths, dtype=np.int64), fed - up._emit[ids])
+        ph = None if hb is None else hb.plan(ids, np.zeros(len(ids), dtype=np.int64), pd.lengths, both, pu, up._emit[ids],
+                                             owed, True)
+        return pd, p16, pc, pu, ph, owed
+
+    def _feed_at(self, parts, lens, ids):
+        """``feed`` at ``fs``: down-resample, the 16 kHz pass on what became ready, up-resample what it returned, and with
+        ``highband`` rejoin the band above 8 kHz.  All plans are made before the first launch, so a refusal leaves every
+        session as it was."""
+        down, up, hb = self._down, self._up, self._hb
+        pd, p16, pu, ph = self._plan_feed_at(lens, ids)
         if not len(ids):
             return []
-        x16 = down.run(pd, down._cat(parts, pd.n_in), ids)
+        packet = down._cat(parts, pd.n_in)
+        x16 = down.run(pd, packet, ids)
         y16 = self._feed16(p16, [x16], ids)
         y = up.run(pu, y16 if pu.n_in else None, ids)
+        if hb is not None:                                      # the band above 8 kHz rejoins what came back (section 3r)
+            y = hb.run(ph, pu, packet, x16 if pd.n_out else None, y16 if pu.n_in else None, y, ids)
         return list(torch.split(y, pu.lengths))                 # back to back in the order of ids
 
     def _close_at(self, ids, tails):
@@ -703,29 +765,21 @@ class StreamPool:
         if tails is not None and any(t is not None and (not torch.is_tensor(t) or t.numel()) for t in tails):
             raise ValueError("close() takes tails at %d Hz; this pool runs at %d Hz, where feed() is the ingress and the "
                              "samples that wait are the tail" % (SAMPLE_RATE, self.fs))
-        down, up = self._down, self._up
-        fed = down._recv[ids].copy()
-        pd = down.plan(np.zeros(len(ids), dtype=np.int64), ids, True)
-        L16 = HOP * self._hops[ids] + self._pend[ids] + np.asarray(pd.lengths, dtype=np.int64)     # = ceil(fed p / q)
-        if (L16 < MIN_SAMPLES).any():
-            i = int(np.argmax(L16 < MIN_SAMPLES))
-            raise ValueError("session %d has %d samples at %d Hz, %d at %d Hz; at least %d are needed there (reflect padding "
-                             "of the first frame)" % (ids[i], fed[i], self.fs, L16[i], SAMPLE_RATE, MIN_SAMPLES))
-        p16 = plan_feed(self._hops, self._pend, np.asarray(pd.lengths, dtype=np.int64), ids)
-        pc = plan_close(p16.hops, p16.pending, ids)
-        both = np.asarray(p16.lengths, dtype=np.int64) + np.asarray(pc.lengths, dtype=np.int64)
-        pu = up.plan(both, ids, True)
+        down, up, hb = self._down, self._up, self._hb
+        pd, p16, _, pu, ph, owed = self._plan_close_at(ids)
         if not len(ids):
             return []
-        sent = up._emit[ids].copy()
         x16 = down.run(pd, None, ids)
         a = self._feed16(p16, [x16], ids)
         b = self._close16(ids, [None] * len(ids))
         pieces = []
         for i, (o, m) in enumerate(zip(p16.out_off, p16.lengths)):
             pieces += [a[HOP * int(o):HOP * int(o) + m], b[i]]
-        y = up.run(pu, torch.cat(pieces), ids)
-        return [y[o:o + min(m, int(n))] for o, m, n in zip(pu.out_off, pu.lengths, fed - sent)]
+        y16 = torch.cat(pieces)
+        y = up.run(pu, y16, ids)
+        if hb is not None:
+            y = hb.run(ph, pu, None, x16 if pd.n_out else None, y16, y, ids)
+        return [y[o:o + int(m)] for o, m in zip(pu.out_off, owed)]
 
     @torch.no_grad()
     def close(self, ids, tails=None):
