@@ -335,7 +335,11 @@ int trunet_checksum_batch(const void* desc, int n, uint64_t* out, void* stream);
 
 /* ProcessAudio.forward (dataset.py:246-272): rectangular-window, centre/reflect STFT (n_fft 512, hop 128)
  * of B utterances -> feat (B*T, C, 257), T = 1 + L/128; C = 3: (norm-dB-mag, sin, cos) (dataset.py:268-270),
- * C = 4: channel 1 is left for trunet_pcen.  mag (B, T, 257) is written when non-NULL. */
+ * C = 4: channel 1 is left for trunet_pcen.  mag (B, T, 257) is written when non-NULL.
+ * Two frames share one transform (here, in the _fl and ragged siblings: frames 2i, 2i+1 of an utterance; in
+ * trunet_stream_features: streams 2i, 2i+1), so a frame's rounding error is proportional to its partner's norm as well as to
+ * its own; a frame whose 512 samples are all exactly zero is exact whatever its partner holds: mag 0, nm -1, (sin, cos) =
+ * (0, 1), as torch.stft has it. */
 int trunet_stft_features(const float* audio, float* feat, float* mag, const float* tw512, int B, int L, int T,
                          int C, void* stream);
 /* pcenfunc (dataset.py:56-76) on mag (B, T, 257); out points at channel 1 of feat, out_stride = C*257 */

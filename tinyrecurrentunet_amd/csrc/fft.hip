@@ -106,8 +106,37 @@ __device__ __forceinline__ cpx load_audio_pair(const float* __restrict__ x, int 
     return make_float2(va, vb);
 }
 
-__device__ __forceinline__ void stage_audio_pair(cpx* sa, const float* __restrict__ x, int t0, int T, int L) {
-    for (int i = threadIdx.x; i < NF; i += 256) sa[i] = load_audio_pair(x, t0, T, L, i);
+// The fp32 transform of a real sequence is Hermitian only to rounding, so split_pair leaves in each frame an error proportional
+// to its PARTNER's norm.  Next to a loud frame an all-zero one (digital silence before an onset, a muted stream beside a talking
+// one) would get |X| ~ 1e-7 ||partner|| where the reference has exactly 0, which PCEN (eps 1e-6) turns into values as large as
+// those of speech, and noise for (sin, cos) where the reference has (0, 1).  So a frame whose 512 staged samples are all exactly
+// zero gets an exactly zero spectrum: every wave notes which real halves it staged a non-zero sample into (bit 0: real, bit 1:
+// imaginary) in its own LDS word, the transform's first barrier publishes the four words, silence_pair reads them after the
+// split.  No barrier of its own; the same in every kernel that pairs two frames, so their bit-for-bit promises hold.
+__device__ __forceinline__ void note_live(int* wl, cpx v0, cpx v1) {
+    const int re = __any(v0.x != 0.f || v1.x != 0.f), im = __any(v0.y != 0.f || v1.y != 0.f);
+    if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = (re ? 1 : 0) | (im ? 2 : 0);
+}
+__device__ __forceinline__ int pair_live(const int* wl) { return wl[0] | wl[1] | wl[2] | wl[3]; }
+__device__ __forceinline__ void silence_pair(int live, cpx& A, cpx& B) {
+    if (!(live & 1)) A = make_float2(0.f, 0.f);
+    if (!(live & 2)) B = make_float2(0.f, 0.f);
+    // The arithmetic behind this must stay the arithmetic of a plain split_pair: with the selects in sight the compiler
+    // contracts sqrtf(re * re + im * im) and the smoother differently from kernel to kernel (fma(re, re, im * im) here,
+    // fma(im, im, re * re) there: the dense and the frames-last kernels were one ulp apart), which ends the bit-for-bit
+    // promises between the entry points.  Opaque registers keep every kernel on the contraction it had.
+    asm volatile("" : "+v"(A.x), "+v"(A.y), "+v"(B.x), "+v"(B.y));
+}
+
+// thread i stages samples i and i + 256 (256 threads)
+__device__ __forceinline__ void stage_pair(cpx* sa, int* wl, cpx v0, cpx v1) {
+    sa[threadIdx.x] = v0;
+    sa[threadIdx.x + 256] = v1;
+    note_live(wl, v0, v1);
+}
+
+__device__ __forceinline__ void stage_audio_pair(cpx* sa, int* wl, const float* __restrict__ x, int t0, int T, int L) {
+    stage_pair(sa, wl, load_audio_pair(x, t0, T, L, (int)threadIdx.x), load_audio_pair(x, t0, T, L, (int)threadIdx.x + 256));
 }
 
 // grid (ceil(T/2), B); feat: (B*T, C, 257); mag (optional): (B, T, 257)
@@ -115,13 +144,16 @@ __global__ __launch_bounds__(256) void stft_features_kernel(const float* __restr
                                                             float* __restrict__ mag_out, const cpx* __restrict__ tw,
                                                             int L, int T, int C) {
     __shared__ cpx sa[NF], sb[NF];
+    __shared__ int wl[4];
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * 2;
-    stage_audio_pair(sa, audio + (size_t)b * L, t0, T, L);
+    stage_audio_pair(sa, wl, audio + (size_t)b * L, t0, T, L);
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    const int live = pair_live(wl);
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx X[2];
         split_pair(Z, k, NF, X[0], X[1]);
+        silence_pair(live, X[0], X[1]);
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             const int t = t0 + f;
@@ -426,17 +458,21 @@ __global__ __launch_bounds__(256) void stft_features_fl_kernel(const float* __re
                                                                int L, int T, int C, int N, int NP) {
     __shared__ cpx sa[NF], sb[NF], stw[NF / 2];
     __shared__ cpx sx[FLG][BINS];
+    __shared__ int wl[2][4];                   // by the parity of the pair: a wave may stage the next pair while another still reads
     const int n0 = blockIdx.x * FLG;
+    int par = 0;
     fl_stage_twiddles(stw, tw);
     fl_each_pair(n0, N, T,
                  [&](int b, int t0, int i) { return load_audio_pair(audio + (size_t)b * L, t0, T, L, i); },
                  [&](int b, int t0, int slot, cpx v0, cpx v1) {
-        sa[threadIdx.x] = v0;
-        sa[threadIdx.x + 256] = v1;
+        stage_pair(sa, wl[par], v0, v1);
         const cpx* Z = fft_lds_t<9, false>(sa, sb, stw);
+        const int live = pair_live(wl[par]);
+        par ^= 1;
         for (int k = threadIdx.x; k < BINS; k += 256) {
             cpx X[2];
             split_pair(Z, k, NF, X[0], X[1]);
+            silence_pair(live, X[0], X[1]);
 #pragma unroll
             for (int f = 0; f < 2; ++f)
                 if (t0 + f < T && slot + f >= 0 && slot + f < FLG) sx[slot + f][k] = X[f];
@@ -598,9 +634,13 @@ __global__ __launch_bounds__(256) void stream_features_kernel(float* __restrict_
                                                               const cpx* __restrict__ tw, int S, int C, int first, float eps,
                                                               float s, float alpha, float delta, float r, float dr) {
     __shared__ cpx sa[NF], sb[NF];
+    __shared__ int wl[4];
     const int s0 = blockIdx.x * 2;
     const bool two = s0 + 1 < S;
-    for (int i = threadIdx.x; i < NF; i += 256) {
+    cpx st[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = threadIdx.x + 256 * h;
         float v[2] = {0.f, 0.f};
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
@@ -609,8 +649,9 @@ __global__ __launch_bounds__(256) void stream_features_kernel(float* __restrict_
             if (chunk) v[f] = (i < NF - HOPF) ? rg[i + HOPF] : chunk[(size_t)(s0 + f) * HOPF + (i - (NF - HOPF))];
             else v[f] = rg[i];
         }
-        sa[i] = make_float2(v[0], v[1]);
+        st[h] = make_float2(v[0], v[1]);
     }
+    stage_pair(sa, wl, st[0], st[1]);
     __syncthreads();                      // every old ring sample has been read before the shifted ring is written
     if (chunk) {
         for (int i = threadIdx.x; i < NF; i += 256) {
@@ -619,9 +660,11 @@ __global__ __launch_bounds__(256) void stream_features_kernel(float* __restrict_
         }
     }
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    const int live = pair_live(wl);
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx X[2];
         split_pair(Z, k, NF, X[0], X[1]);
+        silence_pair(live, X[0], X[1]);
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             if (f == 1 && !two) continue;
@@ -734,6 +777,7 @@ __global__ __launch_bounds__(256) void stream_features_rows_kernel(float* __rest
                                                                    float s, float alpha, float delta, float r, float dr) {
     __shared__ cpx sa[NF], sb[NF];
     __shared__ float xs[POOL_XS];
+    __shared__ int wl[4];
     const int row = blockIdx.x;
     const int* rec = rows + (size_t)row * ROW_INTS;
     const int slot = rec[0], flags = rec[1], crow = rec[6];
@@ -768,19 +812,24 @@ __global__ __launch_bounds__(256) void stream_features_rows_kernel(float* __rest
     }
     const bool first = (flags & TRUNET_ROW_FIRST) != 0;   // frame 0, and frame 1 in the imaginary half
     const int L = a * HOPF + tail, base = a * HOPF - NF;
-    for (int i = threadIdx.x; i < NF; i += 256) {
+    cpx st[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = threadIdx.x + 256 * h;
         const int j = reflect_idx(t * HOPF + i - NF / 2, L) - base;
         float v1 = 0.f;
         if (first) {
             const int j1 = reflect_idx((t + 1) * HOPF + i - NF / 2, L) - base;
             v1 = xs[min(max(j1, 0), POOL_XS - 1)];
         }
-        sa[i] = make_float2(xs[min(max(j, 0), POOL_XS - 1)], v1);
+        st[h] = make_float2(xs[min(max(j, 0), POOL_XS - 1)], v1);
     }
+    stage_pair(sa, wl, st[0], st[1]);
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    const int live = pair_live(wl);
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx X = Z[k], X1 = make_float2(0.f, 0.f);
-        if (first) split_pair(Z, k, NF, X, X1);
+        if (first) { split_pair(Z, k, NF, X, X1); silence_pair(live, X, X1); }
         float nm, sn, cs;
         const float mag = spectral_features(X.x, X.y, nm, sn, cs);
         o[k] = nm;
@@ -900,6 +949,7 @@ __global__ __launch_bounds__(256) void stream_feed_features_kernel(const float* 
                                                                    const int* __restrict__ rows, int n_rows, int n_samples,
                                                                    int slots, const cpx* __restrict__ tw, int C) {
     __shared__ cpx sa[NF], sb[NF];
+    __shared__ int wl[4];
     const int row = blockIdx.x;
     const int* rec = rows + (size_t)row * FEED_INTS;
     const int slot = rec[0], flags = rec[1], voff = rec[3], r0 = rec[4], n = rec[5], poff = rec[6], pair = rec[9];
@@ -910,7 +960,10 @@ __global__ __launch_bounds__(256) void stream_feed_features_kernel(const float* 
     if (voff < 0 || voff > r0 + n - (first ? 3 * HOPF - NF : 0)) return;       // FIRST needs x[0, 384), a frame its 512 samples
     if (first && (pair < 0 || pair >= n_rows || pair == row)) return;
     const FeedLine ln = {ring + (size_t)slot * NF, fifo + (size_t)slot * HOPF, samples + poff, r0, n};
-    for (int i = threadIdx.x; i < NF; i += 256) {
+    cpx st[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = threadIdx.x + 256 * h;
         float v0, v1 = 0.f;
         if (first) {
             v0 = feed_line_at(ln, voff + reflect_idx(i - NF / 2, 3 * HOPF));
@@ -918,14 +971,16 @@ __global__ __launch_bounds__(256) void stream_feed_features_kernel(const float* 
         } else {
             v0 = feed_line_at(ln, voff + i);
         }
-        sa[i] = make_float2(v0, v1);
+        st[h] = make_float2(v0, v1);
     }
+    stage_pair(sa, wl, st[0], st[1]);
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    const int live = pair_live(wl);
     float* o = feat + ((size_t)row * C) * BINS;
     float* o1 = feat + ((size_t)(first ? pair : row) * C) * BINS;
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx X = Z[k], X1 = make_float2(0.f, 0.f);
-        if (first) split_pair(Z, k, NF, X, X1);
+        if (first) { split_pair(Z, k, NF, X, X1); silence_pair(live, X, X1); }
         float nm, sn, cs;
         const float mag = spectral_features(X.x, X.y, nm, sn, cs);
         o[k] = nm;
@@ -1563,20 +1618,19 @@ __global__ __launch_bounds__(256) void stft_features_ragged_kernel(const float* 
                                                                    float* __restrict__ mag_out, const cpx* __restrict__ tw,
                                                                    int B, int64_t nS, int64_t nT, int C) {
     __shared__ cpx sa[NF], sb[NF];
+    __shared__ int wl[4];
     RaggedUtt u;
     int t0;
     if (!ragged_pair(so, fo, po, B, nS, nT, blockIdx.x, u, t0)) return;      // uniform over the workgroup
     const int L = u.L, T = u.T;
     const float* x = audio + u.s0;
-    for (int i = threadIdx.x; i < NF; i += 256) {
-        const float va = x[reflect_idx(t0 * HOPF + i - NF / 2, L)];
-        const float vb = (t0 + 1 < T) ? x[reflect_idx((t0 + 1) * HOPF + i - NF / 2, L)] : 0.f;
-        sa[i] = make_float2(va, vb);
-    }
+    stage_audio_pair(sa, wl, x, t0, T, L);
     const cpx* Z = fft_lds_t<9, false>(sa, sb, tw);
+    const int live = pair_live(wl);
     for (int k = threadIdx.x; k < BINS; k += 256) {
         cpx X[2];
         split_pair(Z, k, NF, X[0], X[1]);
+        silence_pair(live, X[0], X[1]);
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             const int t = t0 + f;
