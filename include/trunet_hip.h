@@ -472,6 +472,37 @@ int trunet_stream_feed_mask_istft(const float* net_out, float* frames, int n_row
 int trunet_stream_feed_ola(const float* frames, float* ola, float* out, const int32_t* rows, const int32_t* sess,
                            const int32_t* seq, int n_sess, int n_rows, int n_out, int slots, void* stream);
 
+/* ---- the attenuation limit (atten.py): out[n] = y[n] + g (x[n] - y[n]) at 16 kHz, directly behind the
+ * overlap-add; y the enhanced sample a route returns, x the dry input sample at the same position, g = 10^(-L / 20) in [0, 1]
+ * (g = 0: out = y bit for bit).  fp32: one subtraction and one fused multiply-add (atten_blend.hpp, shared by all three).
+ * trunet_atten_blend_ragged (enhance): in place on audio (total_samples), the packed iSTFT output; dry: the packed input;
+ *   gains (B): one per utterance; sample_off as in the ragged entry points above.  One launch.
+ * trunet_atten_blend_rows (AudioStream): in place on out[r * out_stride + i], i < n, with dry[r * dry_stride + i] and
+ *   gains[r], r < rows.  One launch.
+ * trunet_stream_atten (StreamPool): per slot dry_line (slots, TRUNET_ATT_DRY_LINE) the samples at 16 kHz fed and not yet
+ *   returned (at most 511), g_cur (slots) the gain the slot's session last emitted with, g_tgt (slots) the gain it is to have
+ *   (written by the host only).  packet (n_packet): the call's new samples back to back; out (n_out): the call's output.
+ *   plan: DEVICE array (n_sess, TRUNET_ATT_INTS) int32, one record per listed session, distinct slots:
+ *     [0] slot   [1] c0: samples in its dry line   [2] offset and [3] length n of its packet   [4] offset and [5] length m of
+ *     its outputs in out (m <= c0 + n)   [6] TRUNET_ATT_FIRST: the call holds frame 0 of the session, which starts at its
+ *     target (g_cur is not read); TRUNET_ATT_CLOSING: the session ends, m = c0 + n and nothing is kept   [7] zero.
+ *   A workgroup per record: with line = [dry_line[slot][0, c0) | packet[[2], [2] + n)], out[[4] + k] = blend(out[[4] + k],
+ *   line[k], g_k), k < m, where g_k = g_tgt[slot], except over k < 128 when g_cur differs from it: g_k = g_cur + (g_tgt -
+ *   g_cur) (k + 1) / 128, g_127 = g_tgt -- the first hop a session emits after a change.  Then dry_line[slot] <- line[m, c0 +
+ *   n) and, when FIRST or m > 0, g_cur[slot] <- g_tgt[slot].  One launch, after the overlap-add on the same stream.
+ * TRUNET_EINVAL without a launch for anything the host can see; a record whose slot, packet, outputs or remainder lie outside
+ * slots, n_packet, n_out or the line is skipped before any load or store. */
+#define TRUNET_ATT_INTS 8
+#define TRUNET_ATT_DRY_LINE 512
+#define TRUNET_ATT_FIRST 1
+#define TRUNET_ATT_CLOSING 2
+int trunet_atten_blend_ragged(float* audio, const float* dry, const float* gains, const int64_t* sample_off, int B,
+                              int64_t total_samples, void* stream);
+int trunet_atten_blend_rows(float* out, const float* dry, const float* gains, int rows, int n, int out_stride, int dry_stride,
+                            void* stream);
+int trunet_stream_atten(float* out, float* dry_line, float* g_cur, const float* g_tgt, const float* packet,
+                        const int32_t* plan, int n_sess, int slots, int n_packet, int n_out, void* stream);
+
 /* ---- offline enhancement of B utterances of any lengths (enhance.py), packed back to back ----
  * audio holds sum L_b samples (L_b >= 257); sample_off[B+1] (prefix of L_b), frame_off[B+1] (prefix of T_b = 1 + L_b/128)
  * and pair_off[B+1] (prefix of ceil(T_b/2)) are int64 DEVICE arrays; total_* are their last entries.  Frames are paired

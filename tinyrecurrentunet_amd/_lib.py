@@ -214,6 +214,9 @@ def _declare(L):
         "trunet_stream_feed_commit": [p, p, p, p, p, p, p, p, i, i, i, i, i, f, f, f, f, f, p],
         "trunet_stream_feed_mask_istft": [p, p, i, p, f, p],
         "trunet_stream_feed_ola": [p, p, p, p, p, p, i, i, i, i, p],
+        "trunet_atten_blend_ragged": [p, p, p, p, i, i64, p],
+        "trunet_atten_blend_rows": [p, p, p, i, i, i, i, p],
+        "trunet_stream_atten": [p, p, p, p, p, p, i, i, i, i, p],
         "trunet_stft_features_ragged": [p, p, p, p, p, p, p, i, i64, i64, i64, i, p],
         "trunet_pcen_ragged": [p, p, p, i, i64, i, f, f, f, f, f, p],
         "trunet_mask_istft_ragged": [p, p, p, p, p, p, p, i, i64, i64, i64, f, p],

@@ -27,6 +27,7 @@ Command line (the ``denoise.py`` role)::
 
     python -m tinyrecurrentunet_amd.enhance --checkpoint CKPT --input-size {3,4} [--use-tgru] --in DIR --out DIR [--resample]
     ... --resample [--highband {drop,keep,follow}] [--highband-floor-db DB]
+    ... --atten-lim-db L        suppress the noise by at most L dB (atten.py)
 """
 import argparse
 import math
@@ -103,7 +104,7 @@ def _inputs(x, lengths):
 
 @torch.no_grad()
 def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAMPLE_RATE, highband="drop",
-            highband_floor_db=-30.0):
+            highband_floor_db=-30.0, atten_lim_db=None):
     """Denoise recordings of any lengths with ``net`` (a ``network.TRUNet`` in eval mode, on the GPU).
 
     x: a list of 1-D fp32 cuda tensors -> list of 1-D tensors of the same lengths; or a (B, Lmax) tensor with ``lengths``
@@ -120,7 +121,12 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     not restored.  "keep": the input's band is added back as it was.  "follow": it is added back attenuated, frame by
     frame, by the suppression the network applied between 4 and 8 kHz, never below ``highband_floor_db`` (at most 0 dB)
     and never amplified (highband.rejoin).  At ``fs`` <= 16 kHz there is no such band: the result is
-    that of "drop"."""
+    that of "drop".
+    atten_lim_db: the most the noise is suppressed, in dB: a number >= 0 or inf, or one per utterance (a sequence or a 1-D
+    tensor).  None (default): no limit, and nothing is added to the call.  With L dB every 16 kHz sample becomes
+    y + g (x - y), g = 10^(-L / 20), y the enhanced and x the input sample (atten.py): one more launch,
+    trunet_atten_blend_ragged, in place on the iSTFT output.  At another ``fs`` the blend acts at 16 kHz, so resampling and
+    ``highband`` read the blended signal, and "follow" holds the band above 8 kHz by the same limit."""
     if path not in PATHS:
         raise ValueError("path must be one of %s, got %r" % (PATHS, path))
     from .highband import check_args
@@ -135,8 +141,12 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     if net.use_tgru and path in ("folded", "int8"):
         raise ValueError("use_tgru runs the layer kernels (frames_per_seq): path=%r carries no sequence" % path)
     if fs != SAMPLE_RATE:
-        return _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband, highband_floor_db)
+        return _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband, highband_floor_db, atten_lim_db)
     xs, width = _inputs(x, lengths)
+    g = None
+    if atten_lim_db is not None:
+        from .atten import gains
+        g = gains(atten_lim_db, len(xs))
     for b, t in enumerate(xs):
         if t.shape[0] < MIN_SAMPLES:
             raise ValueError("utterance %d has %d samples; at least %d are needed (reflect padding of the first frame)"
@@ -157,6 +167,8 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
 
     # 1. pack
     pk = Packed(xs, dev)
+    if g is not None:                             # the gains go up with the offset tables, before the first launch
+        g = torch.from_numpy(g).pin_memory().to(dev, non_blocking=True)
     # 2. features (+ PCEN)
     feat = features(pk, C)
     # 3. network
@@ -180,6 +192,8 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     del feat
     # 4. mask + iSTFT
     den = mask_istft(pk, out, beta)
+    if g is not None:
+        atten_blend(pk, den, g)
     # 5. unpack
     if width is None:
         return list(torch.split(den, pk.lens))
@@ -189,13 +203,17 @@ def enhance(net, x, lengths=None, beta=0.5, max_frames=None, path="auto", fs=SAM
     return Y
 
 
-def _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband="drop", floor_db=-30.0):
+def _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband="drop", floor_db=-30.0, atten_lim_db=None):
     """enhance() for audio at ``fs``: resample -> enhance at 16 kHz -> resample back -> cut to the input lengths.
     ceil(ceil(L p / q) q / p) >= L, so there is always enough to cut.  With ``highband`` "keep" or "follow" and ``fs``
-    above 16 kHz the way back is highband.rejoin, which adds the input's band above 8 kHz to the resampled result."""
+    above 16 kHz the way back is highband.rejoin, which adds the input's band above 8 kHz to the resampled result.  An
+    attenuation limit goes to the 16 kHz call."""
     from . import resample as R
     p, q = R.ratio(fs, SAMPLE_RATE)
     xs, width = _inputs(x, lengths)
+    if atten_lim_db is not None:
+        from .atten import gains
+        gains(atten_lim_db, len(xs))                      # refuse before anything reaches the device
     for b, t in enumerate(xs):
         if R.out_length(t.shape[0], p, q) < MIN_SAMPLES:
             raise ValueError("utterance %d has %d samples at %d Hz, %d at %d Hz; at least %d are needed there (reflect "
@@ -203,7 +221,10 @@ def _enhance_at(net, x, lengths, beta, max_frames, path, fs, highband="drop", fl
                                                               SAMPLE_RATE, MIN_SAMPLES))
     lens = [int(t.shape[0]) for t in xs]
     down = R.resample(xs, fs, SAMPLE_RATE)
-    den = enhance(net, down, beta=beta, max_frames=max_frames, path=path)
+    if atten_lim_db is None:
+        den = enhance(net, down, beta=beta, max_frames=max_frames, path=path)
+    else:
+        den = enhance(net, down, beta=beta, max_frames=max_frames, path=path, atten_lim_db=atten_lim_db)
     if highband != "drop" and p < q and xs:
         from .highband import rejoin
         up = rejoin(xs, down, den, fs, highband, floor_db)
@@ -264,6 +285,16 @@ def mask_istft(pk, out, beta=0.5):
     den = torch.empty(pk.nS, device=pk.dev, dtype=torch.float32)
     check(L.lib().trunet_mask_istft_ragged(ptr(out), ptr(fr), ptr(den), so, fo, po, ptr(L.twiddles(N_FFT, pk.dev)), pk.B,
                                            pk.nS, pk.nT, pk.nP, float(beta), L.stream()), "mask_istft_ragged")
+    return den
+
+
+def atten_blend(pk, den, g):
+    """trunet_atten_blend_ragged: den[n] <- den[n] + g_b (x[n] - den[n]) in place, x the packed input ``pk.audio`` and g
+    the (B,) fp32 gains on the device, one per utterance (atten.gains)"""
+    if tuple(g.shape) != (pk.B,):
+        raise ValueError("expected %d gains, got %s" % (pk.B, tuple(g.shape)))
+    check(L.lib().trunet_atten_blend_ragged(ptr(den), ptr(pk.audio), ptr(g), pk.ptrs()[0], pk.B, pk.nS, L.stream()),
+          "atten_blend_ragged")
     return den
 
 
@@ -332,7 +363,16 @@ def main(argv=None):
                          "network applied between 4 and 8 kHz.  Files at 16 kHz and below are unaffected")
     ap.add_argument("--highband-floor-db", type=float, default=-30.0,
                     help="--highband follow: the most the band above 8 kHz is attenuated, in dB (default -30)")
+    ap.add_argument("--atten-lim-db", type=float, default=None,
+                    help="suppress the noise by at most this many dB (>= 0; default: no limit): every sample becomes "
+                         "y + 10^(-L/20) (x - y), y the enhanced and x the input sample at 16 kHz")
     args = ap.parse_args(argv)
+    if args.atten_lim_db is not None:
+        from .atten import gain
+        try:
+            gain(args.atten_lim_db)
+        except ValueError as e:
+            ap.error(str(e))
     if not args.resample and (args.highband != "drop" or args.highband_floor_db != -30.0):
         ap.error("--highband and --highband-floor-db go with --resample")
     from .highband import check_args
@@ -370,7 +410,7 @@ def main(argv=None):
         for chunk in _batches([xs[i].shape[0] for i in group], max_samples):
             idx = [group[k] for k in chunk]
             ys = enhance(net, [xs[i].cuda() for i in idx], path=args.path, fs=rate, highband=args.highband,
-                         highband_floor_db=args.highband_floor_db)
+                         highband_floor_db=args.highband_floor_db, atten_lim_db=args.atten_lim_db)
             for i, y in zip(idx, ys):
                 q16 = torch.clamp(torch.round(y * 32768.0), -32768, 32767).to(torch.int16).cpu().numpy()
                 wavwrite(os.path.join(args.outdir, names[i]), rate, q16)

@@ -304,7 +304,8 @@ class TRUNet(nn.Module):
         """A ``streaming.StreamPool`` of ``slots`` independent streaming sessions on this network (eval mode): sessions open,
         step, pause and close on their own, at any length from 257 samples; see the class for ``tgru`` / ``beta`` / ``int8`` /
         ``fs`` (packets at 8 to 96 kHz, resampled on the GPU) / ``highband`` (above 16 kHz: the band above 8 kHz kept or
-        following the network's suppression)."""
+        following the network's suppression) / ``atten_lim_db`` (suppress by at most that many dB, per session and movable
+        with ``pool.set_atten_lim``)."""
         from .streaming import StreamPool
         return StreamPool(self, slots, **kw)
 

@@ -10,6 +10,8 @@ block -- the TGRU hidden state.  One hop of 128 new samples per stream costs THR
     trunet_stream_mask_istft phase-aware mask + irFFT-512 + overlap-add tail -> the 128 samples that are final now
 
 All state tensors keep their addresses, so a captured hipGraph of one steady-state step replays hop after hop.
+``AudioStream(..., atten_lim_db=L)`` (a scalar or one value per stream; atten.py) suppresses by at most L
+dB: a fourth launch, trunet_atten_blend_rows, blends each emitted hop with its dry samples, which the ring still holds.
 
 The stream reproduces the OFFLINE path of ``util.loss_fn`` (centred STFT with reflect padding, ``dataset.py:260-264``;
 ``torch.istft``'s envelope normalisation) sample for sample: frame t of the centred STFT covers samples
@@ -40,7 +42,13 @@ PCEN = dict(eps=1e-6, s=0.025, alpha=0.98, delta=2.0, r=0.5)     # dataset.py:56
 
 
 class AudioStream:
-    def __init__(self, net, streams, tgru=False, beta=0.5, device=None, int8=False):
+    def __init__(self, net, streams, tgru=False, beta=0.5, device=None, int8=False, atten_lim_db=None):
+        # atten_lim_db: suppress by at most that many dB (atten.py), a scalar or one value per stream,
+        # fixed for the life of the object.  None: no limit, nothing is added to a hop
+        g = None
+        if atten_lim_db is not None:
+            from .atten import gains
+            g = gains(atten_lim_db, int(streams), "streams")     # refuse before anything reaches the device
         if net.training:
             raise L.TrunetHipError("AudioStream is an inference path: call net.eval() first")
         dev = device if device is not None else next(net.parameters()).device
@@ -66,6 +74,8 @@ class AudioStream:
             self.run = net.folded(tgru=self.tgru)
         self.h = self.run.new_state(self.S, dev) if self.tgru else None      # TGRU state (streams, 128, 16)
         self.tw = L.twiddles(N_FFT, dev)
+        # the streams' gains at a fixed address, so that a captured hop replays with them
+        self.gain = None if g is None else torch.from_numpy(g).to(dev)      # before the first launch: the stream is idle
         self.hops_in = 0                    # hops received
         self.frames = 0                     # STFT frames processed
         self._head = []                     # the first three hops (the reflect-padded first frame needs x[0..256])
@@ -88,7 +98,17 @@ class AudioStream:
         env = 4.0 if t >= 3 else float(t + 1)
         check(lib.trunet_stream_mask_istft(ptr(y), ptr(self.ola), ptr(out), ptr(self.tw), self.S, self.beta, env, st),
               "stream_mask_istft")
-        return out if t >= 2 else None
+        if t < 2:
+            return None
+        # frame t covers samples [128 t - 256, 128 t + 256): the ring starts with the dry samples of hop t - 2
+        self._blend(out, 0)
+        return out
+
+    def _blend(self, out, ring_off):
+        """the attenuation limit on a (S, 128) hop whose dry samples are ring[:, ring_off:ring_off + 128]: one launch"""
+        if self.gain is not None:
+            check(L.lib().trunet_atten_blend_rows(ptr(out), self.ring.data_ptr() + 4 * ring_off, ptr(self.gain), self.S, HOP,
+                                                  HOP, N_FFT, L.stream()), "atten_blend_rows")
 
     def push(self, chunk):
         """chunk: (streams, 128) new samples per stream (fp32, on the GPU).  Returns (streams, 128 k) denoised samples,
@@ -133,7 +153,9 @@ class AudioStream:
             outs.append(self._frame(tail[:, :HOP].contiguous()))
             outs.append(self._frame(tail[:, HOP:].contiguous()))
             # the last hop is covered by three frames only, all of them done: it sits at the head of the overlap-add tail
-            outs.append(self.ola[:, :HOP] / 3.0)
+            last = self.ola[:, :HOP] / 3.0
+            self._blend(last, HOP)                              # the ring is x[L - 256, L) and its reflection by now
+            outs.append(last)
         outs = [o for o in outs if o is not None]
         return torch.cat(outs, 1)
 
@@ -370,8 +392,9 @@ class StreamPool:
     """A fixed number of independent streaming sessions on the single-launch forward.
 
         pool = StreamPool(net, slots, tgru=None, beta=0.5, int8=False, fs=16000,   # net in eval mode on the GPU; tgru None: net.use_tgru
-                          highband="drop", highband_floor_db=-30.0)
+                          highband="drop", highband_floor_db=-30.0, atten_lim_db=None)
         ids = pool.open(n)                      # n free slot ids
+        pool.set_atten_lim(ids, L)              # a pool built with atten_lim_db: move sessions' attenuation limit (dB)
         out, valid = pool.step(chunks, ids)     # chunks (n, 128) fp32 cuda; ids: n distinct open slots
         rest = pool.close(ids, tails)           # list of 1-D tensors; tails[i]: the 0..127 last samples of session i, or None
         pool.abort(ids)                         # drop sessions without output
@@ -447,18 +470,34 @@ class StreamPool:
     ``highband.MODES`` and a floor outside (-inf, 0] are a ValueError before anything reaches the device; at ``fs`` <= 16 kHz
     the arguments are validated and the pool is that of ``"drop"``; a rate whose per-slot line cannot be bounded inside
     4096 samples (above 120 kHz) is refused at construction.  ``step`` and ``close`` with a tail stay a ValueError at these
-    rates."""
+    rates.
+
+    ``atten_lim_db`` (keyword only; ``pool.atten_lim_db``): the attenuation limit a session opens with (atten.py, DESIGN
+    section 3s): every 16 kHz sample the pool returns becomes y + g (x - y), g = 10^(-L / 20), y the enhanced and x the input
+    sample.  None, the default: the pool above bit for bit, with no blend stage, no allocation and no launch of it.  A pool
+    built with a limit (``inf`` for "none yet") takes ``pool.set_atten_lim(ids, L)`` for open sessions at any time: over the
+    first hop a session emits after the call its gain goes linearly from the old value to the new one, so where the ramp
+    lies follows from the samples fed so far, not from how they were cut into packets; a session whose frame 0 is still to
+    come starts at the new value, and a slot's next session at the pool's limit again.  Per slot the pool then also keeps a
+    dry line, the samples fed and not yet returned (at most 511), the gain the session last emitted with and its target;
+    ``step``, ``feed`` and ``close`` add ONE launch each (trunet_stream_atten, after the overlap-add; two in a ``close`` at
+    another rate), its records travel with the call's plan, and ``set_atten_lim`` is one copy of the slots' targets.  The
+    blend sits in the 16 kHz pass: at another ``fs`` the up-resampler, ``"keep"`` and the ``"follow"`` gain read the blended
+    signal.  Everything above holds with a limit: packets do not matter, pool-mates and their limits do not matter."""
 
     def __init__(self, net, slots, tgru=None, beta=0.5, int8=False, fs=SAMPLE_RATE, *, highband="drop",
-                 highband_floor_db=-30.0):
+                 highband_floor_db=-30.0, atten_lim_db=None):
+        from . import atten as AT
         from . import highband as HB
         HB.check_args(highband, highband_floor_db)               # before anything touches the network or the device
+        if atten_lim_db is not None:
+            AT.gain(atten_lim_db)
         if net.training:
             raise L.TrunetHipError("StreamPool is an inference path: call net.eval() first")
         dev = next(net.parameters()).device
         if dev.type != "cuda":
             raise L.TrunetHipError("tinyrecurrentunet_amd runs on MI355X only: the network sits on %s" % dev)
-        self._host_init(slots, fs, dev, highband, highband_floor_db)
+        self._host_init(slots, fs, dev, highband, highband_floor_db, atten_lim_db)
         self.tgru = bool(net.use_tgru if tgru is None else tgru)
         self.net, self.beta, self.dev = net, float(beta), dev
         self.C = net.encoder[0].StandardConv1d[0].in_channels
@@ -480,13 +519,17 @@ class StreamPool:
         self.fifo = z(S, HOP)                                    # feed(): the 0..127 samples that wait for their hop to fill
         self.tw = L.twiddles(N_FFT, dev)
 
-    def _host_init(self, slots, fs, dev, highband="drop", highband_floor_db=-30.0):
+    def _host_init(self, slots, fs, dev, highband="drop", highband_floor_db=-30.0, atten_lim_db=None):
         """the host side of a pool: the slot allocator, the per-slot counters and, at another rate than 16 kHz, the two
         stream resamplers (whose device buffers come with their first launch); above 16 kHz with ``highband`` "keep" or
-        "follow", the state that carries the band above 8 kHz.  No device work."""
+        "follow", the state that carries the band above 8 kHz; with ``atten_lim_db`` the gain a session
+        opens with and the host's copy of every slot's target gain (section 3s).  No device work."""
+        from . import atten as AT
         from . import highband as HB
         from . import resample as R
         self.highband, self.highband_floor_db = HB.check_args(highband, highband_floor_db)
+        self.atten_lim_db = atten_lim_db
+        self._g_open = None if atten_lim_db is None else AT.gain(atten_lim_db)
         R.ratio(fs, SAMPLE_RATE)
         self._alloc = SlotAllocator(slots)
         S = self._alloc.capacity
@@ -494,6 +537,10 @@ class StreamPool:
         self._hops = np.zeros(S, dtype=np.int64)
         self._pend = np.zeros(S, dtype=np.int64)                 # samples in the FIFO, per slot
         self._down = self._up = self._hb = None
+        # the attenuation limit: target gain per slot (host copy; the device's is brought up to date before it is read),
+        # and the device state (dry line, current and target gain per slot), which comes with the first launch
+        self._g_tgt = None if self._g_open is None else np.full(S, self._g_open, dtype=np.float32)
+        self._g_stale, self._att_state = self._g_open is not None, None
         if self.fs != SAMPLE_RATE:
             self._down = R.StreamResampler(self.fs, SAMPLE_RATE, S, dev)
             self._up = R.StreamResampler(SAMPLE_RATE, self.fs, S, dev)
@@ -525,8 +572,87 @@ class StreamPool:
         for i in ids:
             self._hops[i] = 0
             self._pend[i] = 0
+        if self._g_open is not None and len(ids):               # a session opens with the pool's limit, whatever the
+            self._g_tgt[ids] = self._g_open                      # slot's last session was given
+            self._g_stale = True
         self._reset_rate(ids)
         return ids
+
+    # ---- the attenuation limit
+    def set_atten_lim(self, ids, atten_lim_db):
+        """Move the limit of open sessions while they run: ids n distinct open slots, atten_lim_db a scalar or one value per
+        id (dB >= 0 or inf).  Over the first hop a session emits after the call its gain goes linearly from the old value to
+        the new one, then stays there; a session whose frame 0 is still to come starts at the new value.  One small host
+        -> device copy (the slots' target gains), no synchronisation.  ValueError, with nothing changed, for a pool built
+        without ``atten_lim_db`` (it has no blend stage), ids that are not open and values ``atten.gain`` refuses."""
+        from . import atten as AT
+        if self._g_open is None:
+            raise ValueError("this pool was built without atten_lim_db and has no blend stage: give StreamPool a limit "
+                             "(inf for none) to move it per session")
+        ids = self._ids(ids)
+        g = AT.gains(atten_lim_db, len(ids), "sessions")
+        if not len(ids):
+            return
+        self._g_tgt[ids] = g
+        self._g_stale = True
+        self._push_targets()
+
+    def _att(self):
+        """the per-slot device state of the blend stage: dry line, current gain, target gain"""
+        from . import atten as AT
+        if self._att_state is None:
+            S, z = self.capacity, lambda *s: torch.zeros(s, device=self.dev, dtype=torch.float32)
+            self._att_state = (z(S, AT.DRY_LINE), z(S), z(S))
+        return self._att_state
+
+    def _push_targets(self):
+        """the slots' target gains, host -> device, when the host's copy has moved: staged in pinned memory of its own and
+        copied asynchronously, so the host does not wait for the stream and a later change cannot reach an earlier copy"""
+        if self._g_stale:
+            self._att()[2].copy_(torch.from_numpy(self._g_tgt).pin_memory(), non_blocking=True)
+            self._g_stale = False
+
+    def _dry_count(self, ids):
+        """samples of each listed session fed and not yet returned: a hop comes back four hops after it arrived"""
+        return HOP * np.minimum(self._hops[ids], 3) + self._pend[ids]
+
+    # the blend stage's records of a call (``atten.plan_atten``), host only, from the counters BEFORE the call; None for a
+    # pool without a limit
+    def _att_step(self, ids, plan):
+        """``step``: the hop that came is the packet, row pos of (n, 128) the output where valid; frame 0 at hop three"""
+        if self._g_open is None:
+            return None
+        from .atten import plan_atten
+        at = HOP * np.arange(len(ids))
+        return plan_atten(ids, self._dry_count(ids), at, np.full(len(ids), HOP), at, HOP * plan.valid, plan.hops == 3, False)[0]
+
+    def _att_feed(self, plan):
+        """``feed``: one record per session in the order of ``plan.sess``; None also for a call that moves nothing"""
+        if self._g_open is None or not (plan.n_samples or plan.n_out):
+            return None
+        from .atten import plan_atten
+        sl, order = plan.sess[:, 0].astype(np.int64), plan.sess[:, 9].astype(np.int64)
+        return plan_atten(sl, self._dry_count(sl), plan.sess[:, 7], plan.sess[:, 6], HOP * np.asarray(plan.out_off)[order],
+                          np.asarray(plan.lengths, dtype=np.int64)[order], (plan.sess[:, 1] & ROW_FIRST) != 0, False)[0]
+
+    def _att_close(self, ids, plan, tails, rs):
+        """``close``: the packet is row i of the (n, 128) tails, read only for a tail that was given (a fed session's
+        already waits in its dry line); the output row i of (n, 512); frame 0 for a session of two hops"""
+        if self._g_open is None:
+            return None
+        from .atten import plan_atten
+        n = len(ids)
+        return plan_atten(ids, self._dry_count(ids), HOP * np.arange(n), [0 if t is None else r for t, r in zip(tails, rs)],
+                          CLOSE_OUT_ROWS * HOP * np.arange(n), plan.lengths, self._hops[ids] < 3, True)[0]
+
+    def _atten(self, table, packet, n_packet, out, n_out):
+        """trunet_stream_atten over the records ``table`` (device, ``atten.plan_atten``): the call's output, blended in
+        place, and the slots' dry lines and current gains moved on.  One launch."""
+        dry, g_cur, g_tgt = self._att()
+        self._push_targets()
+        check(L.lib().trunet_stream_atten(ptr(out) if n_out else None, ptr(dry), ptr(g_cur), ptr(g_tgt),
+                                          ptr(packet) if n_packet else None, table.data_ptr(), table.shape[0], self.capacity,
+                                          n_packet, n_out, L.stream()), "stream_atten")
 
     def abort(self, ids):
         """Drop sessions without output; the slots are free again."""
@@ -587,12 +713,16 @@ class StreamPool:
         check(lib.trunet_stream_mask_istft_rows(ptr(y), ptr(self.ola), ptr(out), rows.data_ptr(), nf, n_out, self.capacity,
                                                 ptr(self.tw), self.beta, st), "stream_mask_istft_rows")
 
-    def _run_passes(self, plan, chunks, n_chunks, out, n_out):
-        dev_tab = torch.from_numpy(np.concatenate(plan.tables)).to(self.dev)     # the row tables of every pass: ONE copy
+    def _run_passes(self, plan, chunks, n_chunks, out, n_out, att=None):
+        """att: the records of the blend stage (``atten.plan_atten``; they travel with the row tables), or None"""
+        tabs = plan.tables if att is None else plan.tables + [att]
+        dev_tab = torch.from_numpy(np.concatenate(tabs)).to(self.dev)           # the row tables of every pass: ONE copy
         r0 = 0
         for table, nf in zip(plan.tables, plan.frames):
             self._pass(dev_tab[r0:r0 + len(table)], table, nf, chunks, n_chunks, out, n_out)
             r0 += len(table)
+        if att is not None:
+            self._atten(dev_tab[r0:], chunks, n_chunks * HOP, out, n_out * HOP)
 
     @torch.no_grad()
     def step(self, chunks, ids):
@@ -616,7 +746,7 @@ class StreamPool:
             return out, torch.zeros(0, dtype=torch.bool)
         chunks = chunks.contiguous().float()
         plan = plan_step(self._hops, ids)
-        self._run_passes(plan, chunks, len(ids), out, len(ids))
+        self._run_passes(plan, chunks, len(ids), out, len(ids), self._att_step(ids, plan))
         self._hops[ids] = plan.hops
         return out, torch.from_numpy(plan.valid)
 
@@ -679,10 +809,13 @@ class StreamPool:
         if plan.n_samples:
             parts = [t for t in parts if t.shape[0]]
             samples = (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous().float()
-        tab = torch.from_numpy(np.concatenate([plan.rows.reshape(-1), plan.sess.reshape(-1), plan.seq])).to(dev)   # ONE copy
+        host_tabs, att = [plan.rows.reshape(-1), plan.sess.reshape(-1), plan.seq], self._att_feed(plan)
+        if att is not None:                                     # the blend stage's records travel with the plan
+            host_tabs.append(att.reshape(-1))
+        tab = torch.from_numpy(np.concatenate(host_tabs)).to(dev)              # ONE copy
         rows = tab[:n_rows * FEED_INTS].view(n_rows, FEED_INTS)
         sess = tab[n_rows * FEED_INTS:(n_rows + n_sess) * FEED_INTS]
-        seq = tab[(n_rows + n_sess) * FEED_INTS:]
+        seq = tab[(n_rows + n_sess) * FEED_INTS:(n_rows + n_sess) * FEED_INTS + n_rows]
         prow, pseq = (rows.data_ptr(), seq.data_ptr()) if n_rows else (None, None)
         feat = None
         if n_rows:
@@ -705,6 +838,9 @@ class StreamPool:
             check(lib.trunet_stream_feed_ola(ptr(frames), ptr(self.ola), ptr(out) if plan.n_out else None, prow,
                                              sess.data_ptr(), pseq, plan.n_active, n_rows, plan.n_out, S, st),
                   "stream_feed_ola")
+        if att is not None:
+            self._atten(tab[(n_rows + n_sess) * FEED_INTS + n_rows:].view(n_sess, -1), samples, plan.n_samples, out,
+                        plan.n_out * HOP)
         self._hops[ids] = plan.hops
         self._pend[ids] = plan.pending
         return out
@@ -829,6 +965,6 @@ class StreamPool:
             where = np.concatenate([HOP * i + np.arange(rs[i]) for i in given])
             tl.view(-1).index_copy_(0, torch.from_numpy(where).to(self.dev), torch.cat([tails[i].float() for i in given]))
         out = torch.zeros((n, CLOSE_OUT_ROWS * HOP), device=self.dev, dtype=torch.float32)
-        self._run_passes(plan, tl, n_tl, out, n * CLOSE_OUT_ROWS)
+        self._run_passes(plan, tl, n_tl, out, n * CLOSE_OUT_ROWS, self._att_close(ids, plan, tails, rs))
         self._alloc.release(ids)
         return [out[i, :m] for i, m in enumerate(plan.lengths)]
