@@ -12,6 +12,9 @@ show that the comparison would catch a subtly wrong kernel); None everywhere els
 import torch
 
 MUTANTS = ("bhn_outside", "dzp_ht", "rev_forwards", "no_carry", "dghn_dnp", "swap_u4", "k_half", "hs_off")
+# FGRU only, for the bf16-octet kernels of bf16_gru.hip (tests/bgru_ref.py): a bf16 rounding INSIDE the recurrence, where
+# those kernels keep fp32 -- h rounded before it is carried into the next step, dgh rounded in front of the carry product
+BF16_MUTANTS = ("h_rounded", "dgh_rounded")
 
 
 def _swap_u4(t, axis):
@@ -43,6 +46,8 @@ def fgru_fwd(gi, whh, bhh, dtype=torch.float64, mut=None):
                 n = torch.tanh(g[2 * H:] + r * ghn)
             h = (1 - z) * n + z * h
             hout[d * H:(d + 1) * H, pos] = h
+            if mut == "h_rounded":
+                h = h.bfloat16().to(dtype)
             for k, v in enumerate((r, z, n, ghn)):
                 gates[d, k, :, pos] = v
     if mut == "swap_u4":
@@ -75,7 +80,9 @@ def fgru_bwd(dhout, hout, gates, whh, dtype=torch.float64, mut=None):
             dgi[d * 3 * H:(d + 1) * 3 * H, pos] = torch.cat((drp, dzp, dnp))
             dghn[d * H:(d + 1) * H, pos] = dgn
             carry = dh * z
-            if mut != "no_carry":
+            if mut == "dgh_rounded":
+                carry = carry + whh[d].t() @ torch.cat((drp, dzp, dnp * r)).bfloat16().to(dtype)
+            elif mut != "no_carry":
                 carry = carry + whh[d].t() @ torch.cat((drp, dzp, dnp * r))
     if mut == "swap_u4":
         dgi, dghn = _swap_u4(dgi, 0), _swap_u4(dghn, 0)
@@ -156,6 +163,15 @@ def gru_cell(gi, gh, h, dtype=torch.float64):
     return (1 - z) * n + z * h, torch.stack((r, z, n, gh[2 * H:]))
 
 
+def bound(ref64, ref32):
+    """What `close` allows a kernel, from the references alone: e32 = max|fp32 restatement - fp64|, the bound
+    4 e32 + 2e-6 max|fp64| on the maximum error, rel32 = relative L2 of the same difference, and 4 rel32 + 1e-6 on the
+    relative L2.  Returns (e32, bound, rel32, rel_bound)."""
+    d32 = ref32.double() - ref64
+    e32, rel32 = float(d32.abs().max()), float(d32.norm()) / (float(ref64.norm()) + 1e-300)
+    return e32, 4 * e32 + 2e-6 * float(ref64.abs().max()), rel32, 4 * rel32 + 1e-6
+
+
 def close(got, ref64, ref32, what):
     """The one comparison of the GRU tests.  The tolerance is measured on the same inputs, against the reference and never
     against the kernel: e32 = max|fp32 restatement - fp64|, rel32 = relative L2 of the same difference.  Required:
@@ -166,13 +182,9 @@ def close(got, ref64, ref32, what):
     assert ref64.dtype == torch.float64 and got.shape == ref64.shape == ref32.shape, (what, got.shape, ref64.shape)
     assert bool(torch.isfinite(got).all()), "%s: not finite" % what
     assert bool(torch.isfinite(ref64).all()) and bool(torch.isfinite(ref32).all()), "%s: reference not finite" % what
-    d32 = ref32.double() - ref64
     d = got.double() - ref64
-    nrm = float(ref64.norm()) + 1e-300
-    e32, rel32 = float(d32.abs().max()), float(d32.norm()) / nrm
-    err, rel = float(d.abs().max()), float(d.norm()) / nrm
-    bound = 4 * e32 + 2e-6 * float(ref64.abs().max())
-    rbound = 4 * rel32 + 1e-6
-    assert err <= bound, "%s: max error %.3e > bound %.3e (e32 %.3e)" % (what, err, bound, e32)
+    e32, bnd, rel32, rbound = bound(ref64, ref32)
+    err, rel = float(d.abs().max()), float(d.norm()) / (float(ref64.norm()) + 1e-300)
+    assert err <= bnd, "%s: max error %.3e > bound %.3e (e32 %.3e)" % (what, err, bnd, e32)
     assert rel <= rbound, "%s: relative L2 %.3e > bound %.3e (rel32 %.3e)" % (what, rel, rbound, rel32)
-    return err, e32, bound, rel, rbound
+    return err, e32, bnd, rel, rbound
